@@ -7,12 +7,20 @@ batch 32 per GPU of 1x256x256 synthetic magnitude spectrograms, bf16 compute
 (f32 master weights / statistics / gradients).  A frame is one STFT column, so
 one spectrogram = 256 frames.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints one JSON line.  After the timed steps, an instrumented repeat
-of the same steps records HIP events around every launch of each op class
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K
+steps and prints the headline figures (``value``, ``ms_per_step`` = wall time
+of the K timed steps / K).  ``--dump-outputs DIR`` also writes what the last
+timed step computed (its loss, the model output, a fixed seeded sample of the
+updated parameters) as float32 ``DIR/<name>.npy``; the inputs, the weights
+and the dropout seeds are fixed by the arguments, so two builds can be
+compared output for output.
+
+Everything else runs only under ``--full`` (and adds its fields to the same
+line).  After the timed steps, an instrumented repeat of the same steps records HIP events around every launch of each op class
 (functional.timed) on the stream it runs on; ``op_table`` lists each class's
 GPU time per step and algorithmic FLOP/s (or bytes/s) against its roofline,
 and ``roofline`` is the class with the most GPU time (the ViT linear
@@ -28,6 +36,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -50,7 +59,13 @@ def parse():
                          "reducer's finish) in a hipGraph and replay it; 0: eager launches.  Default 1")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 32; 16 for --variant large)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the host enqueue cost, the eager step, the per-op "
+                         "roofline table (instrumented repeat + graph-timed dominant class) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (loss, model output, a seeded sample of the updated "
+                         "parameters) as float32 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--mode", default="train", choices=["train", "infer"],
                     help="infer: BASELINE config 2 (forward only, eval, no grad)")
@@ -322,11 +337,15 @@ def main():
     if args.mode == "infer":
         model.eval()
 
+    last_y = [None]  # the latest step's model output (a reference only; --dump-outputs reads it)
+
     def step():
         if args.mode == "infer":
             with torch.no_grad():
-                return model(noisy).float().mean()
+                y = last_y[0] = model(noisy)
+                return y.float().mean()
         y = model(noisy)
+        last_y[0] = y.detach()
         loss = crit(y, clean)
         loss.backward()
         if reducer is not None:
@@ -404,7 +423,70 @@ def main():
     value = spectros * FRAMES
     if not torch.isfinite(loss).item():
         raise RuntimeError("non-finite loss")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, args.mode, loss, last_y[0], model)
+    final_loss = loss.item()  # the last timed step's (a graph's loss buffer is rewritten by the --full repeats)
 
+    extra = full_measurements(args, step, eager_step, graph, ms, world, rank) if args.full else {}
+    if rank == 0:
+        out = {
+            "metric": ("spectrogram-frames/sec/GPU (fwd+bwd) on 256x256 mag-spec, batch 32; 1/2/4/8 GPU"
+                       if args.mode == "train" else "spectrogram-frames/sec/GPU (fwd only, eval) on 256x256 mag-spec"),
+            "value": round(value, 1),
+            "unit": "spectrogram-frames/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms, 3),
+            "ms_per_step_median": round(ms_median, 3),
+            "launch": "hipGraph replay of the whole step" if graph is not None else "eager",
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": args.precision + ("+fp8-attention" if args.attn == "fp8" else ""),
+            "data": "synthetic (harmonic+noise 16 kHz waveforms, host STFT 512/128 hann, min-max, 256x256)",
+            "config": {"workload": (("HybridViT default (enc 64/128/256, 6x8-head d512 ViT, dec 256/128/64/1)"
+                                     if args.variant == "default" else
+                                     "HybridViT large (enc 64/128/256, 12x12-head d768 ViT, dec 256/128/64/1)")
+                                    + (" train step: fwd + CombinedLoss + bwd + clip + AdamW" if args.mode == "train"
+                                       else " inference forward (eval, no grad)")),
+                       "global_batch": world * args.batch, "seq_len": 256, "input": [args.batch, 1, 256, 256],
+                       "parallelism": f"dp{world}",
+                       "dist_backend": dist.get_backend() if use_dist else None},
+            "spectrograms_per_s": round(spectros, 2),
+            "frames_per_s_per_gpu": round(value / world, 1),
+            "value_is": "aggregate spectrogram frames/s over all n_gpus (per-GPU figure: frames_per_s_per_gpu)",
+            "final_loss": round(final_loss, 6),
+            "full": bool(args.full),
+        }
+        out.update(extra)
+        print(json.dumps(out), flush=True)
+    if use_dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, mode, loss, y, model):
+    """What the last timed step handed back, as float32 ``path/<name>.npy``:
+    its loss (train) or output mean (infer), the model output, and the values
+    of the parameters after the step at 2^20 positions of their concatenation
+    drawn from a fixed seed (a sample keeps the dump at 12 MB for the default
+    workload, whatever the variant's parameter count)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {("loss" if mode == "train" else "output_mean"): loss.detach().float().reshape(1),
+              "output": y.detach().float()}
+    if mode == "train":
+        flat = torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])
+        g = torch.Generator().manual_seed(1234)
+        idx = torch.randint(0, flat.numel(), (min(flat.numel(), 1 << 20),), generator=g).sort().values
+        arrays["params_sample"] = flat[idx.to(flat.device)]
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
+
+
+def full_measurements(args, step, eager_step, graph, ms, world, rank):
+    """The --full part of the result line: host enqueue cost, the eager step,
+    the per-op table, the dominant class's roofline and the CPU baseline."""
     # host enqueue cost of one step while the GPU queue is busy (no sync inside)
     HF = sys.modules["hvit_amd.functional"]
     step()
@@ -451,7 +533,6 @@ def main():
     table = op_table(HF.OP_TIMES, isteps)
     HF.OP_TIMES = None
 
-    out = None
     roof = roofline_of(table) if rank == 0 else None
     if world == 1 and roof is not None:
         # the dominant class re-timed as a graph replay of its recorded launches (no per-launch events)
@@ -470,52 +551,20 @@ def main():
                          "measured": "HIP events around a hipGraph replay of this op class's launches recorded "
                                      "from one real step (10 repetitions; no per-launch events -- the instrumented "
                                      "repeat's per-launch event figure in event_avg_launch_us / event_frac)"})
-    if rank == 0:
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.mode == "train" and args.variant == "default":
-            cpu = cpu_baseline(args.batch, args.cpu_seconds)
-        out = {
-            "metric": ("spectrogram-frames/sec/GPU (fwd+bwd) on 256x256 mag-spec, batch 32; 1/2/4/8 GPU"
-                       if args.mode == "train" else "spectrogram-frames/sec/GPU (fwd only, eval) on 256x256 mag-spec"),
-            "value": round(value, 1),
-            "unit": "spectrogram-frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms, 3),
-            "ms_per_step_median": round(ms_median, 3),
-            "launch": "hipGraph replay of the whole step" if graph is not None else "eager",
-            "ms_per_step_eager": round(eager_ms, 3) if eager_ms is not None else round(ms, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.precision + ("+fp8-attention" if args.attn == "fp8" else ""),
-            "data": "synthetic (harmonic+noise 16 kHz waveforms, host STFT 512/128 hann, min-max, 256x256)",
-            "config": {"workload": (("HybridViT default (enc 64/128/256, 6x8-head d512 ViT, dec 256/128/64/1)"
-                                     if args.variant == "default" else
-                                     "HybridViT large (enc 64/128/256, 12x12-head d768 ViT, dec 256/128/64/1)")
-                                    + (" train step: fwd + CombinedLoss + bwd + clip + AdamW" if args.mode == "train"
-                                       else " inference forward (eval, no grad)")),
-                       "global_batch": world * args.batch, "seq_len": 256, "input": [args.batch, 1, 256, 256],
-                       "parallelism": f"dp{world}",
-                       "dist_backend": dist.get_backend() if use_dist else None},
-            "spectrograms_per_s": round(spectros, 2),
-            "frames_per_s_per_gpu": round(value / world, 1),
-            "value_is": "aggregate spectrogram frames/s over all n_gpus (per-GPU figure: frames_per_s_per_gpu)",
-            "host_enqueue_ms_per_step": round(host_ms, 3),
-            "host_enqueue_is": "graph replay call" if graph is not None else "eager launches of one step",
-            "final_loss": round(loss.item(), 6),
-            "roofline": roof,
-            "op_table": {k: {kk: vv for kk, vv in v.items() if kk != "work_per_launch"} for k, v in table.items()},
-            "op_table_sum_ms_per_step": round(sum(v["ms_per_step"] for v in table.values()), 3),
-            "op_table_is": "eager instrumented repeat: HIP events around every op class and every other C-ABI call "
-                           "('abi:' rows); the sum covers the whole step's kernels",
-            "cpu_baseline": cpu,
-        }
-        print(json.dumps(out), flush=True)
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    res = {
+        "ms_per_step_eager": round(eager_ms, 3) if eager_ms is not None else round(ms, 3),
+        "host_enqueue_ms_per_step": round(host_ms, 3),
+        "host_enqueue_is": "graph replay call" if graph is not None else "eager launches of one step",
+        "roofline": roof,
+        "op_table": {k: {kk: vv for kk, vv in v.items() if kk != "work_per_launch"} for k, v in table.items()},
+        "op_table_sum_ms_per_step": round(sum(v["ms_per_step"] for v in table.values()), 3),
+        "op_table_is": "eager instrumented repeat: HIP events around every op class and every other C-ABI call "
+                       "('abi:' rows); the sum covers the whole step's kernels",
+        "cpu_baseline": None,
+    }
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "train" and args.variant == "default":
+        res["cpu_baseline"] = cpu_baseline(args.batch, args.cpu_seconds)
+    return res
 
 
 if __name__ == "__main__":

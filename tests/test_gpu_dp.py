@@ -134,7 +134,7 @@ def test_rccl_world1_bench_dp_branch():
     env = dict(os.environ, HVIT_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--steps", "3",
-           "--warmup", "1", "--batch", "4", "--no-cpu-baseline"]
+           "--warmup", "1", "--batch", "4", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     # (the first error lines name the failing call; the tail holds the launcher's report)
     errs = [ln for ln in r.stderr.splitlines() if "rror" in ln or "what()" in ln or "fault" in ln.lower()][:20]

@@ -1,4 +1,4 @@
-"""Print the op table of a bench.py JSON line: tools/opt.py LOG [LOG2] (side by side)."""
+"""Print the op table of a bench.py --full JSON line: tools/opt.py LOG [LOG2] (side by side)."""
 import json
 import sys
 
