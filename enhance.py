@@ -12,8 +12,10 @@ defaults with a warning (enhance.py:105-110); its ``model`` section feeds
 ``create_hybrid_vit`` and its ``audio`` section the enhancer's STFT settings
 (:131-138); ``--extension`` picks the files of directory mode (:160-165).
 Additions: ``--config`` (one more YAML merged on top), ``--synthetic``,
-``--precision``.  STFT / iSTFT on the host; the HybridViT forward on the GPU
-(HIP path, fp32 unless --precision bf16).
+``--precision``, ``--frontend`` and ``--batch-size``.  STFT / iSTFT on the host
+by default, on the GPU with ``--frontend device`` (directory mode then batches
+``--batch-size`` clips per forward); the HybridViT forward on the GPU (HIP path,
+fp32 unless --precision bf16).
 """
 
 import argparse
@@ -38,6 +40,9 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--no-normalize", action="store_true")
+    ap.add_argument("--frontend", default="host", choices=["host", "device"],
+                    help="where STFT / iSTFT run: torch on the host (default) or the HIP kernels on the GPU")
+    ap.add_argument("--batch-size", type=int, default=1, help="clips per forward in directory mode")
     a = ap.parse_args(argv)
     single = a.input is not None and a.output is not None
     directory = a.input_dir is not None and a.output_dir is not None
@@ -67,7 +72,8 @@ def main(argv=None):
         ap.error("--checkpoint is required unless --synthetic is given")
     au = cfg.get("audio", {}) or {}
     enh = E.AudioEnhancer(model, device=a.device, sample_rate=au.get("sample_rate", 16000), n_fft=au.get("n_fft", 512),
-                          hop_length=au.get("hop_length", 128), win_length=au.get("win_length", 512))
+                          hop_length=au.get("hop_length", 128), win_length=au.get("win_length", 512),
+                          frontend=a.frontend)
     norm = not a.no_normalize
     if a.synthetic is not None:
         torch.manual_seed(0)
@@ -80,7 +86,8 @@ def main(argv=None):
     elif single:
         enh.enhance_file(a.input, a.output, normalize=norm)
     else:
-        enh.enhance_directory(a.input_dir, a.output_dir, extension=a.extension, normalize=norm)
+        enh.enhance_directory(a.input_dir, a.output_dir, extension=a.extension, normalize=norm,
+                              batch_size=a.batch_size)
 
 
 if __name__ == "__main__":

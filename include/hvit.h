@@ -488,6 +488,42 @@ int hvit_adamw_dev(int count, const hvit_adamw_item_t* items, const hvit_adamw_h
 int hvit_rng_advance(unsigned long long* state, unsigned long long* seed_out, void* stream);
 int hvit_step_bump(float* steps, int n, float inc, void* stream);
 
+/* STFT / iSTFT framing around the model (librosa.stft / librosa.istft with
+ * center=True, zero padding, a window centred in n_fft, T = 1 + len / hop:
+ * utils/audio_processing.py:67-98 and :101-131, inference/enhancer.py:82-89
+ * and :111-118, data/dataset.py:183-190), f32.  Supported: n_fft 256, 512 or
+ * 1024 and n_fft / 8 <= hop <= n_fft / 2.  window is the [n_fft] f32 table
+ * (a shorter window already centred in it by the caller).  lengths (int32 [B],
+ * nullable: every row is L long) gives each row's sample count; row b is
+ * wave[b, :len_b] followed by zeros, whatever the buffer holds past len_b.
+ *
+ * hvit_stft_fwd: wave [B, L] (row stride wave_stride elements) ->
+ *   mag [B, F, T] (F = n_fft / 2 + 1, T = 1 + L / hop contiguous: the model's
+ *   [B, 1, F, T] input), phasor [B, F, T, 2] (nullable) = the unit complex
+ *   X / |X|, exactly (1, 0) where |X| == 0 (enhancer.py:91-93 keeps the angle;
+ *   only mag' * e^{j phase} is ever formed from it), stats [B, 2] (nullable) =
+ *   {min, max} of mag over the row's valid frames t < 1 + len_b / hop, which
+ *   the call initialises itself.  Frames at or past the valid count are
+ *   written as mag = 0, phasor = (1, 0).
+ * hvit_spec_normalize, in place on mag [B, F, T] from such stats: mode 0 =
+ *   mag / max if max > 1e-8 (enhancer.py:96-101), mode 1 = (mag - min) /
+ *   (max - min) if max > min (data/dataset.py:213-219); frames past a row's
+ *   valid count (from lengths and hop; all T when lengths is NULL) stay 0.
+ * hvit_istft: wave_out [B, L] row b = istft(gain_b * mag_b * phasor_b, length =
+ *   len_b) followed by zeros (enhancer.py:108-118): the imaginary parts of the
+ *   DC and Nyquist bins are ignored and the inverse scales by 1 / n_fft as
+ *   numpy.fft.irfft does, only the first min(T, ceil((len_b + n_fft) / hop))
+ *   frames are used, and the overlap-added sum is divided by the window-square
+ *   envelope of those frames where it exceeds FLT_MIN.  gain: nullable device
+ *   f32 [B].  Every output sample gathers its frames in ascending order (no
+ *   float atomics): results are bit-identical from run to run. */
+int hvit_stft_fwd(const float* wave, long long wave_stride, const int* lengths, int B, int L, int n_fft, int hop,
+                  const float* window, int T, float* mag, float* phasor, float* stats, void* stream);
+int hvit_spec_normalize(float* mag, int B, int F, int T, const int* lengths, int hop, const float* stats, int mode,
+                        void* stream);
+int hvit_istft(const float* mag, const float* phasor, const float* gain, const int* lengths, int B, int F, int T,
+               int hop, const float* window, int L, float* wave_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

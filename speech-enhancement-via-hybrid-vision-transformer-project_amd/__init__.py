@@ -7,7 +7,8 @@ plus the factory it forgot to export):
     PatchEmbedding, PositionalEncoding, MultiHeadSelfAttention,
     TransformerEncoderBlock, VisionTransformer, CombinedLoss, create_loss_function,
     FusedAdamW / clip_grad_norm_ / create_optimizer (training/optimizer.py, trainer.py:170-174),
-    GraphedTrainStep (the train step replayed from a hipGraph per input shape, trainer.py:142-183)
+    GraphedTrainStep (the train step replayed from a hipGraph per input shape, trainer.py:142-183),
+    stft_mag / istft_mag / supported / n_frames (the device STFT / iSTFT front end, frontend.py)
 """
 
 from .hybrid_vit import (  # noqa: F401
@@ -27,11 +28,12 @@ from .losses import CombinedLoss, create_loss_function  # noqa: F401
 from .optim import FusedAdamW, clip_grad_norm_, create_optimizer  # noqa: F401
 from .train_step import GraphedTrainStep  # noqa: F401
 from .config import load_all_configs, load_config, merge_configs  # noqa: F401
+from .frontend import istft_mag, n_frames, stft_mag, supported  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = [
     "HybridViT", "create_hybrid_vit", "ConvBlock", "TransposeConvBlock", "FeedForward", "PatchEmbedding",
     "PositionalEncoding", "MultiHeadSelfAttention", "TransformerEncoderBlock", "VisionTransformer",
     "CombinedLoss", "create_loss_function", "FusedAdamW", "clip_grad_norm_", "create_optimizer", "GraphedTrainStep",
-    "load_all_configs", "load_config", "merge_configs",
+    "load_all_configs", "load_config", "merge_configs", "stft_mag", "istft_mag", "supported", "n_frames",
 ]

@@ -164,6 +164,9 @@ _SIGS = {
     "hvit_gemm_tune": ([i32, i32], i32),
     "hvit_probe_gemm_splitk": ([i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, vp], i32),
     "hvit_step_bump": ([vp, i32, f32, vp], i32),
+    "hvit_stft_fwd": ([vp, i64, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp], i32),
+    "hvit_spec_normalize": ([vp, i32, i32, i32, vp, i32, vp, i32, vp], i32),
+    "hvit_istft": ([vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp], i32),
 }
 
 EXPORTED = sorted(k for k in _SIGS)

@@ -6,7 +6,9 @@ phase, a 5 Hz envelope, peak 0.8, plus N(0, 0.15^2) noise for the noisy copy.
 Spectrograms use the reference's host STFT settings (n_fft 512, hop 128,
 win 512, periodic Hann, center=True; inference/enhancer.py:82-89,
 data/dataset.py:183-190) and per-utterance min-max scaling
-(data/dataset.py:213-219).  STFT/iSTFT stay on the host (north star).
+(data/dataset.py:213-219).  The framing runs on the host by default (north
+star); ``spectrogram_batch(..., device=...)`` runs it and the scaling on the GPU
+as one batch (frontend.py, csrc/stft.hip).
 """
 
 from __future__ import annotations
@@ -43,9 +45,22 @@ def minmax(m: torch.Tensor) -> torch.Tensor:
     return (m - lo) / (hi - lo) if hi > lo else m
 
 
-def spectrogram_batch(batch: int, freq: int = 256, frames: int = 256, seed: int = 1234):
-    """(noisy, clean) magnitude batches [B, 1, freq, frames] in [0, 1]."""
+def spectrogram_batch(batch: int, freq: int = 256, frames: int = 256, seed: int = 1234, device=None):
+    """(noisy, clean) magnitude batches [B, 1, freq, frames] in [0, 1].
+
+    ``device=None`` (default) frames every clip on the host with torch.stft.
+    With a GPU device the waveforms are still synthesised on the host, but the
+    framing and min-max scaling of all 2 B clips run as one batch through
+    frontend.stft_mag(normalize="minmax") and the result stays on the device."""
     n = (frames - 1) * HOP
+    if device is not None:
+        from .frontend import stft_mag
+
+        pairs = [harmonic_pair(n, seed + i) for i in range(batch)]
+        wave = np.stack([p[1] for p in pairs] + [p[0] for p in pairs])
+        m = stft_mag(torch.from_numpy(wave).to(device), None, N_FFT, HOP, WIN, normalize="minmax")
+        m = m[:, :, :freq, :frames]
+        return m[:batch].contiguous(), m[batch:].contiguous()
     noisy, clean = [], []
     for i in range(batch):
         c, nz = harmonic_pair(n, seed + i)

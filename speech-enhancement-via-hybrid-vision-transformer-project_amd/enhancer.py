@@ -4,8 +4,11 @@ with the same call surface -- ``enhance``, ``enhance_file``,
 ``enhance_directory``, ``enhance_audio``, ``enhance_file`` (module level) and
 ``load_model_for_inference``.
 
-STFT / iSTFT framing stays on the host, as the north star says.  librosa is
-not available here, so the framing is ``torch.stft`` / ``torch.istft`` with the
+STFT / iSTFT framing runs on the host by default (``frontend="host"``), as the
+north star says; ``frontend="device"`` moves it to the HIP kernels of
+frontend.py (csrc/stft.hip, f32), where a batch of clips goes waveform ->
+spectrogram -> model -> waveform on the device (``enhance_batch``).  librosa is
+not available here, so the host framing is ``torch.stft`` / ``torch.istft`` with the
 reference's settings (n_fft 512, hop 128, win 512, periodic Hann,
 center=True, constant padding -- librosa >= 0.10's ``pad_mode`` default;
 enhancer.py:82-89, :111-118).  tests/test_enhancer.py checks both against a
@@ -36,7 +39,18 @@ class AudioEnhancer:
     """inference/enhancer.py:15-56 (constructor) and :57-135 (enhance)."""
 
     def __init__(self, model: nn.Module, device: str = "cuda", sample_rate: int = 16000, n_fft: int = 512,
-                 hop_length: int = 128, win_length: int = 512, window: str = "hann"):
+                 hop_length: int = 128, win_length: int = 512, window: str = "hann", frontend: str = "host"):
+        if frontend not in ("host", "device"):
+            raise ValueError(f"hvit enhancer: frontend {frontend!r} ('host' or 'device')")
+        if frontend == "device":
+            from . import frontend as FE
+
+            if window != "hann":
+                raise ValueError(f"hvit enhancer: the device front end has no window {window!r} (only 'hann')")
+            if not FE.supported(n_fft, hop_length, win_length):
+                raise ValueError(f"hvit enhancer: the device front end does not support n_fft={n_fft}, "
+                                 f"hop_length={hop_length}, win_length={win_length}")
+        self.frontend = frontend
         self.model = model.to(device).eval()
         self.device = device
         self.sample_rate = sample_rate
@@ -58,6 +72,8 @@ class AudioEnhancer:
     @torch.no_grad()
     def enhance(self, noisy_audio: np.ndarray, normalize: bool = True) -> np.ndarray:
         noisy_audio = np.asarray(noisy_audio, dtype=np.float32)
+        if self.frontend == "device":
+            return self._enhance_device([noisy_audio], normalize)[0]
         max_val = 1.0
         if normalize:
             mv = float(np.abs(noisy_audio).max()) if noisy_audio.size else 0.0
@@ -78,6 +94,66 @@ class AudioEnhancer:
             out = out * max_val
         return out.astype(np.float32)
 
+    @torch.no_grad()
+    def _enhance_device(self, clips, normalize: bool):
+        """Clips of one frame count through the device front end as one batch:
+        host peak normalisation, one upload, stft_mag (max-normalised) ->
+        model -> istft_mag with gain = mag_max * max_val taken from the
+        kernel's stats on the device (no read-back before the download)."""
+        from . import frontend as FE
+
+        lens = [int(c.size) for c in clips]
+        out = [np.zeros(0, dtype=np.float32) if n == 0 else None for n in lens]
+        idx = [i for i, n in enumerate(lens) if n > 0]
+        if not idx:
+            return out
+        Lmax = max(lens[i] for i in idx)
+        wave = np.zeros((len(idx), Lmax), dtype=np.float32)
+        peak = np.ones(len(idx), dtype=np.float32)
+        for r, i in enumerate(idx):
+            c = clips[i]
+            if normalize:
+                mv = float(np.abs(c).max())
+                if mv > 1e-8:
+                    c = c / mv
+                    peak[r] = mv
+            wave[r, :lens[i]] = c
+        dev = torch.device(self.device)
+        w = torch.from_numpy(wave).to(dev)
+        ln = torch.as_tensor([lens[i] for i in idx], dtype=torch.int32).to(dev)
+        pk = torch.from_numpy(peak).to(dev)
+        mag, phasor, stats = FE.stft_mag(w, ln, self.n_fft, self.hop_length, self.win_length, return_phasor=True,
+                                         normalize="max")
+        enh = self.model(mag)
+        enh = enh.reshape(mag.shape).float().contiguous()
+        mx = stats[:, 1]
+        gain = torch.where(mx > 1e-8, mx, torch.ones_like(mx)) * pk
+        y = FE.istft_mag(enh, phasor, ln, gain, self.hop_length, self.win_length, length=Lmax).cpu().numpy()
+        for r, i in enumerate(idx):
+            out[i] = y[r, :lens[i]].copy()
+        return out
+
+    def enhance_batch(self, clips, normalize: bool = True, batch_size: int = 32):
+        """Enhance a list of clips; results in input order.  Clips are grouped
+        by frame count ``1 + len // hop`` and, within a group, right-zero-padded
+        to the longest member (exact: with constant padding a zero-extended row
+        has the same frames); each group runs as forwards of at most
+        ``batch_size`` clips.  With the host front end this loops ``enhance``."""
+        clips = [np.asarray(c, dtype=np.float32) for c in clips]
+        if self.frontend == "host":
+            return [self.enhance(c, normalize=normalize) for c in clips]
+        batch_size = max(1, int(batch_size))
+        groups = {}
+        for i, c in enumerate(clips):
+            groups.setdefault(1 + c.size // self.hop_length, []).append(i)
+        out = [None] * len(clips)
+        for _, members in sorted(groups.items()):
+            for s in range(0, len(members), batch_size):
+                part = members[s:s + batch_size]
+                for i, y in zip(part, self._enhance_device([clips[i] for i in part], normalize)):
+                    out[i] = y
+        return out
+
     def enhance_file(self, input_path: Union[str, Path], output_path: Union[str, Path],
                      normalize: bool = True) -> None:
         audio = read_wav(input_path, self.sample_rate)
@@ -88,12 +164,21 @@ class AudioEnhancer:
         print(f"Enhanced audio saved to {output_path}")
 
     def enhance_directory(self, input_dir: Union[str, Path], output_dir: Union[str, Path], extension: str = ".wav",
-                          normalize: bool = True) -> None:
+                          normalize: bool = True, batch_size: int = 1) -> None:
         files = sorted(Path(input_dir).glob(f"*{extension}"))
         Path(output_dir).mkdir(parents=True, exist_ok=True)
         print(f"Found {len(files)} audio files to enhance")
-        for f in files:
-            self.enhance_file(f, Path(output_dir) / f.name, normalize=normalize)
+        if batch_size > 1:
+            for s in range(0, len(files), batch_size):
+                part = files[s:s + batch_size]
+                outs = self.enhance_batch([read_wav(f, self.sample_rate) for f in part], normalize=normalize,
+                                          batch_size=batch_size)
+                for f, o in zip(part, outs):
+                    write_wav(Path(output_dir) / f.name, o, self.sample_rate)
+                    print(f"Enhanced audio saved to {Path(output_dir) / f.name}")
+        else:
+            for f in files:
+                self.enhance_file(f, Path(output_dir) / f.name, normalize=normalize)
         print(f"All files enhanced and saved to {output_dir}")
 
 
