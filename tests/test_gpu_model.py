@@ -135,6 +135,97 @@ def test_bf16_path(hv, name, kw):
     assert abs(gq.double().norm().item() - float(g[f"gnorm.{qk}"])) < 0.1 * float(g[f"gnorm.{qk}"])
 
 
+@pytest.mark.parametrize("name,kw", [("tiny_odd", O.TINY), ("tiny_clip", O.TINY),
+                                     ("tiny_cls", dict(O.TINY, use_cls_token=True))])
+def test_bf16_path_odd_geometry_and_cls(hv, name, kw):
+    """test_bf16_path's bars at the geometries it leaves out: odd F x T (33x47,
+    257x251: ragged conv tiles, a floor in both max-pools, the final bilinear
+    resize) and a CLS token.  The bf16 eval forward under no_grad (the fused
+    inference forms: BatchNorm folded, ReLU / tanh in the conv epilogue, fc1
+    storing gelu(h) only; the pooling block's 8 input channels keep it on the
+    unfused fallback) and with grad enabled (the unfused eval path), each against
+    the reference's golden output; then a bf16 train step's loss."""
+    g = golden(name)
+    m = build(hv, kw, "bf16", False).eval()
+    x = torch.as_tensor(g["x"]).cuda()
+    with torch.no_grad():
+        y_fused = m(x)
+    y_plain = m(x).detach()
+    assert tuple(y_fused.shape) == tuple(g["eval_out"].shape) == tuple(y_plain.shape)
+    e_fused, e_plain = rel(y_fused.cpu(), g["eval_out"]), rel(y_plain.cpu(), g["eval_out"])
+    print(f"{name}: bf16 eval max-rel vs golden: no_grad {e_fused:.2e}, grad enabled {e_plain:.2e}")
+    assert e_fused < BF16_TOL
+    assert e_plain < BF16_TOL
+    m = build(hv, kw, "bf16", True).train()
+    y = m(x)
+    loss = hv.CombinedLoss()(y, torch.as_tensor(g["target"]).cuda())
+    loss.backward()
+    print(f"{name}: bf16 train loss {loss.item():.6f} vs {float(g['train_loss']):.6f}")
+    assert abs(loss.item() - float(g["train_loss"])) < 2e-2 * abs(float(g["train_loss"]))
+    for k, p in m.named_parameters():
+        assert p.grad is not None and torch.isfinite(p.grad).all(), k
+
+
+def test_bf16_inference_unpooled_fallback_vs_oracle(hv):
+    """The default model on a [2, 1, 250, 94] spectrogram, bf16 eval under
+    no_grad, against the fp32 CPU oracle (closed-form weights) at the bf16 bar.
+    The first block halves 250x94 to 125x47, so the pooling block enc1 (64
+    channels) sees odd H and W: the pooled conv epilogue cannot apply and
+    ConvBNActFn.forward falls back to the plain conv + bn_act there (P = 11750
+    output pixels, no multiple of any tile), while enc2 and the decoder blocks
+    still take the folded conv + ReLU on ragged tiles (62x23, 15x5 tokens)."""
+    cfg = O.HViTConfig()
+    shapes = O.state_dict_shapes(cfg)
+    W = CF.weights(shapes)
+    x = torch.as_tensor(CF.spectrogram((2, 1, 250, 94), 84))
+    m = build(hv, {}, "bf16", False).eval()
+    with torch.no_grad():
+        y = m(x.cuda()).cpu()
+        _, skips = m.forward_encoder(x.cuda())
+        yo = O.forward(O.make_state(shapes, W, requires_grad=False), x, cfg)
+    # enc1's input (= skip 0) is odd in both dimensions: ConvBNActFn.forward's ``pooled`` is False for it
+    assert m.encoder[1].pool == 2 and m.encoder[1].conv.weight.shape[1] % 64 == 0
+    assert tuple(skips[0].shape[2:]) == (125, 47)
+    assert tuple(skips[1].shape[2:]) == (62, 23) and tuple(skips[2].shape[2:]) == (62, 23)
+    assert (2 * 125 * 47) % 64 != 0 and (2 * 62 * 23) % 64 != 0
+    assert m.last_num_tokens == 15 * 5
+    assert tuple(y.shape) == tuple(yo.shape) == (2, 1, 250, 94)
+    e = rel(y, yo)
+    print(f"250x94 bf16 no_grad vs oracle: max-rel {e:.2e}")
+    assert e < BF16_TOL
+
+
+def test_forward_encoder_folds_batchnorm_itself(hv):
+    """forward_encoder under no_grad runs no multi-tensor weight preparation:
+    with nothing prepared ConvBNActFn folds each block's BatchNorm itself
+    (hvit_bn_eval_prep + hvit_bn_fold), bit-identical to the forward's
+    prepared weights (hvit_weight_prep kind 3), on the pooled block and the
+    plain one; and each skip stays at the bf16 bar of the reference's golden
+    encoder outputs."""
+    import importlib
+
+    HF = importlib.import_module("hvit_amd.functional")
+    g = golden("tiny_64")
+    x256 = torch.as_tensor(golden("default_256")["x"]).cuda()
+    m = build(hv, {}, "bf16", False).eval()
+    with torch.no_grad():
+        m(x256)
+        assert HF._prep_get(m.encoder[1].conv.weight, 3, hv._lib.BF16) is not None
+        _, warm = m.forward_encoder(x256)
+        warm = [t.clone() for t in warm]
+        HF.prep_cache_clear()
+        _, cold = m.forward_encoder(x256)
+    assert tuple(warm[1].shape) == (2, 128, 64, 64)  # the pooled form applied
+    for a, b in zip(warm, cold):
+        assert torch.equal(a, b)
+    mt = build(hv, O.TINY, "bf16", False).eval()
+    with torch.no_grad():
+        HF.prep_cache_clear()
+        _, skips = mt.forward_encoder(torch.as_tensor(g["x"]).cuda())
+    for i, sk in enumerate(skips):
+        assert rel(sk.float().cpu(), g[f"eval_enc{i}"]) < BF16_TOL, i
+
+
 def test_long_clip_bf16_vs_oracle(hv):
     """A ~4 s clip: the default model on a [1, 1, 256, 496] spectrogram, 496
     tokens -- the register-resident attention's chunked N > 256 forward (8-wave
@@ -239,6 +330,34 @@ def test_inference_reuses_prepared_weights_until_they_change(hv):
     m.eval()
     with torch.no_grad():
         assert torch.equal(m(x), y2)
+
+
+def test_inference_sees_inplace_batchnorm_edits(hv):
+    """The BN-folded weights kept between inference forwards are valid only for
+    the BatchNorm tensors they were folded from: an in-place edit of a BN
+    weight (gamma), a BN bias (beta) or a running_mean -- in the pooling encoder
+    block, a plain encoder block and a decoder block -- makes the next no_grad
+    forward differ and equal a fresh model's with the same state, bit for bit."""
+    m = build(hv, {}, "bf16", False).eval()
+    g = golden("default_256")
+    x = torch.as_tensor(g["x"]).cuda()
+    edits = [("gamma", m.encoder[1].bn.weight), ("beta", m.encoder[2].bn.bias),
+             ("running_mean", m.decoder[1].bn.running_mean), ("gamma (decoder)", m.decoder[0].bn.weight),
+             ("running_mean (pooling block)", m.encoder[1].bn.running_mean)]
+    with torch.no_grad():
+        y_prev = m(x)
+        assert torch.equal(m(x), y_prev)
+        for what, t in edits:
+            t.mul_(1.25).add_(0.125)
+            y = m(x)
+            fresh = build(hv, {}, "bf16", False).eval()
+            fresh.load_state_dict(m.state_dict())
+            y_fresh = fresh(x)
+            assert not torch.equal(y, y_prev), what
+            assert torch.equal(y, y_fresh), what
+            # (the fresh model's forward replaced the cache: this one fills it with m's weights again)
+            y_prev = m(x)
+            assert torch.equal(y_prev, y), what
 
 
 def test_autocast_selects_bf16(hv):
