@@ -155,9 +155,18 @@ int hvit_linear_wgrad_tk(int dt, const void* dy, const void* x, int M, int N, in
  * hvit_wgrad_workspace); what 4 = the attention backward for bf16 / head_dim 64 /
  * N <= 256 (1: the single-pass kernel, 0: the dQ and dK/dV kernel pair); what 5
  * = the fp8 attention forward form (1: v2, 0: round 4's kernel, 2: v2 as two
- * 8-wave workgroups per (b, h)).
+ * 8-wave workgroups per (b, h)); what 9 = the A operand of the bf16 3x3 conv
+ * forward / data-gradient GEMMs (0: per-tap implicit im2col, 1: the input halo
+ * resident in LDS where it applies and measured faster, 2: wherever it
+ * applies; results are bit-identical); what 10 = read-only, the number of
+ * halo-resident launches so far.
  * Returns the previous value (-1 for an unknown knob). */
 int hvit_gemm_tune(int what, int value);
+/* Diagnostics (tests): the LDS byte offset of the 16-byte channel chunk `chunk`
+ * of halo pixel (hy, hx) in the halo-resident conv A image of a `rows`-row tile
+ * on an H x W map of C channels (csrc/gemm_conv_halo.h), or -1 where that form
+ * does not apply to the geometry.  No GPU work. */
+int hvit_conv_halo_off(int H, int W, int C, int rows, int hy, int hx, int chunk);
 /* Diagnostics only (tools/wgrad_layout_probe.py): C[M,N] = sum_k A[m,k] B[n,k]
  * as f32 split-K slabs ws[splits][M*N + M]; kca / kcb: 1 = operand stored with
  * K contiguous ([M][K] / [N][K]), 0 = [K][M] / [K][N]; cfg 0 = gemm.h's kernels,

@@ -1243,6 +1243,75 @@ __device__ __forceinline__ TileId tile_of(int remap) {
   return {mt, rem - mt * gy, z};
 }
 
+// BatchNorm partial of one 64-row sub-tile, shared by gemm_kernel's plain-store / generic
+// epilogues and the halo-resident conv kernel (gemm_conv_halo.h), whose partials must stay
+// bit-identical: thread (r0, c4) of a 256-thread group holds its output values sv[i] of rows
+// r0 + i*RSTEP, columns 4 c4 .. 4 c4 + 3, and their sums st_sum; Cs is the group's staging
+// image, reused as scratch; tile = the sub-tile's index (row / 64); n = the thread's first column.
+template <int BN, int RSTEP, int NR>
+__device__ __forceinline__ void bn_tile_stats(float* stats, float* Cs, int rows_here, int r0, int c4, int n, int N,
+                                              long tile, const float (&st_sum)[4], const f32x4 (&sv)[NR]) {
+  // per-column (mean, M2) of this 64-row sub-tile.  Each thread holds its
+  // rows r0 + i*RSTEP (i < cnt) of 4 columns in registers: local mean and
+  // M2 there; the RSTEP partials of a column are then merged by one thread
+  // per column (r0 < 4 picks column n + r0), 128 columns in parallel.  Full
+  // halves (every partial over NR rows) merge without divisions:
+  //   mean = sum(m_k) / RSTEP,  M2 = sum(M2_k) + NR sum((m_k - mean)^2);
+  // ragged ones by Chan's pairwise rule.  (A single-wave sequential merge
+  // with IEEE divisions cost ~1.5 us per tile, 34 us of the enc1 conv.)
+  const bool fullh = rows_here == 64;  // uniform
+  const int cnt = fullh ? NR : (rows_here > r0 ? min(NR, (rows_here - r0 + RSTEP - 1) / RSTEP) : 0);
+  const float inv = fullh ? 1.f / (float)NR : (cnt ? 1.f / (float)cnt : 0.f);
+  float mean[4], q[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) mean[e] = st_sum[e] * inv;
+#pragma unroll
+  for (int i = 0; i < NR; ++i)
+    if (fullh || i < cnt)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float d = sv[i][e] - mean[e];
+        q[e] += d * d;
+      }
+  float* red = Cs;  // [2][RSTEP][BN]; the tile's LDS image is no longer read
+  epi_barrier();
+  *(f32x4*)(red + r0 * BN + c4 * 4) = (f32x4){mean[0], mean[1], mean[2], mean[3]};
+  *(f32x4*)(red + (RSTEP + r0) * BN + c4 * 4) = (f32x4){q[0], q[1], q[2], q[3]};
+  epi_barrier();
+  if (r0 < 4 && n + r0 < N) {
+    const int col = c4 * 4 + r0;
+    float mk[RSTEP], qs = 0.f, mu = 0.f, m2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < RSTEP; ++k) {
+      mk[k] = red[k * BN + col];
+      qs += red[(RSTEP + k) * BN + col];
+    }
+    if (fullh) {
+#pragma unroll
+      for (int k = 0; k < RSTEP; ++k) mu += mk[k];
+      mu *= 1.f / (float)RSTEP;
+      float dd = 0.f;
+#pragma unroll
+      for (int k = 0; k < RSTEP; ++k) dd += (mk[k] - mu) * (mk[k] - mu);
+      m2 = qs + (float)NR * dd;
+    } else {
+      float na = 0.f;
+      m2 = qs;
+#pragma unroll
+      for (int k = 0; k < RSTEP; ++k) {
+        const int ck = rows_here > k ? min(NR, (rows_here - k + RSTEP - 1) / RSTEP) : 0;
+        if (ck == 0) continue;
+        const float nn = na + (float)ck, wb = (float)ck / nn;
+        const float d = mk[k] - mu;
+        mu += d * wb;
+        m2 += d * d * (na * wb);
+        na = nn;
+      }
+    }
+    *(float2*)(stats + (tile * N + n + r0) * 2) = make_float2(mu, m2);
+  }
+}
+
 // DMAK: 0 = register-staged K loop, 2 = LDS-DMA with two stage buffers (two
 // workgroups per CU), 1 = LDS-DMA with one stage buffer (three per CU), 3 =
 // three stage buffers (long K, 128x64 / 64x64 tiles)
@@ -1727,68 +1796,8 @@ __global__ __launch_bounds__(GEMM_THREADS, (DMAK == 1 ? 3 : BM >= 128 ? HVIT_BIG
       if (all_in) rows(std::false_type());
       else rows(std::true_type());
     }
-    if (ep.stats && rows_here > 0) {
-      // per-column (mean, M2) of this 64-row sub-tile.  Each thread holds its
-      // rows r0 + i*RSTEP (i < cnt) of 4 columns in registers: local mean and
-      // M2 there; the RSTEP partials of a column are then merged by one thread
-      // per column (r0 < 4 picks column n + r0), 128 columns in parallel.  Full
-      // halves (every partial over NR rows) merge without divisions:
-      //   mean = sum(m_k) / RSTEP,  M2 = sum(M2_k) + NR sum((m_k - mean)^2);
-      // ragged ones by Chan's pairwise rule.  (A single-wave sequential merge
-      // with IEEE divisions cost ~1.5 us per tile, 34 us of the enc1 conv.)
-      const bool fullh = rows_here == 64;  // uniform
-      const int cnt = fullh ? NR : (rows_here > r0 ? min(NR, (rows_here - r0 + RSTEP - 1) / RSTEP) : 0);
-      const float inv = fullh ? 1.f / (float)NR : (cnt ? 1.f / (float)cnt : 0.f);
-      float mean[4], q[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) mean[e] = st_sum[e] * inv;
-#pragma unroll
-      for (int i = 0; i < NR; ++i)
-        if (fullh || i < cnt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float d = sv[i][e] - mean[e];
-            q[e] += d * d;
-          }
-      float* red = Cs;  // [2][RSTEP][BN]; the tile's LDS image is no longer read
-      epi_barrier();
-      *(f32x4*)(red + r0 * BN + c4 * 4) = (f32x4){mean[0], mean[1], mean[2], mean[3]};
-      *(f32x4*)(red + (RSTEP + r0) * BN + c4 * 4) = (f32x4){q[0], q[1], q[2], q[3]};
-      epi_barrier();
-      if (r0 < 4 && n + r0 < N) {
-        const int col = c4 * 4 + r0;
-        float mk[RSTEP], qs = 0.f, mu = 0.f, m2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < RSTEP; ++k) {
-          mk[k] = red[k * BN + col];
-          qs += red[(RSTEP + k) * BN + col];
-        }
-        if (fullh) {
-#pragma unroll
-          for (int k = 0; k < RSTEP; ++k) mu += mk[k];
-          mu *= 1.f / (float)RSTEP;
-          float dd = 0.f;
-#pragma unroll
-          for (int k = 0; k < RSTEP; ++k) dd += (mk[k] - mu) * (mk[k] - mu);
-          m2 = qs + (float)NR * dd;
-        } else {
-          float na = 0.f;
-          m2 = qs;
-#pragma unroll
-          for (int k = 0; k < RSTEP; ++k) {
-            const int ck = rows_here > k ? min(NR, (rows_here - k + RSTEP - 1) / RSTEP) : 0;
-            if (ck == 0) continue;
-            const float nn = na + (float)ck, wb = (float)ck / nn;
-            const float d = mk[k] - mu;
-            mu += d * wb;
-            m2 += d * d * (na * wb);
-            na = nn;
-          }
-        }
-        const long tile = (m0 / 64) + hh;
-        *(float2*)(ep.stats + (tile * N + n + r0) * 2) = make_float2(mu, m2);
-      }
-    }
+    if (ep.stats && rows_here > 0)
+      bn_tile_stats<BN, RSTEP, NR>(ep.stats, Cs, rows_here, r0, c4, n, N, (long)(m0 / 64) + hh, st_sum, sv);
   }
   if (ep.colsum) {
     float* red = Cs + 64 * CP;
@@ -1849,6 +1858,21 @@ inline int& dma_depth_ref() {
 inline int dma_depth() { return dma_depth_ref(); }
 constexpr int DEEP_MIN_STAGES = 16;
 
+// tile: 128x128 when the grid still fills the chip; 128x64 for narrow
+// outputs (N <= 64: conv layers with 64 channels); else 64x64
+inline int auto_tile(int M, int N, int splits) {
+  // 128x64 also when 128x128 would leave fewer than ~1.5 workgroups per CU
+  // or a half-empty last column tile (measured: 2.5 % per train step)
+  constexpr int policy = 2;  // (policies 0 / 1 measured slower: DESIGN.md §8)
+  const long b128 = (long)cdiv(M, 128) * cdiv(N, 128) * splits;
+  const long b12864 = (long)cdiv(M, 128) * cdiv(N, 64) * splits;
+  if (N <= 64 && (long)cdiv(M, 128) * splits >= 160) return 12864;
+  if (policy >= 1 && N > 64 && b128 < 384 && b12864 >= 384) return 12864;
+  if (policy >= 2 && N > 64 && N % 128 != 0 && N % 64 == 0 && b12864 >= 160) return 12864;
+  if (N > 64 && b128 >= 160) return 128;
+  return 64;
+}
+
 template <typename T, class LA, class LB>
 int launch_gemm(LA la, LB lb, int M, int N, int K, int splits, const Epi& ep_in, hipStream_t st,
                 int force_tile = 0) {
@@ -1867,21 +1891,7 @@ int launch_gemm(LA la, LB lb, int M, int N, int K, int splits, const Epi& ep_in,
     hvit_set_error("launch_gemm: split-K requires EPI_SLAB");
     return HVIT_ERR_ARG;
   }
-  // tile: 128x128 when the grid still fills the chip; 128x64 for narrow
-  // outputs (N <= 64: conv layers with 64 channels); else 64x64
-  int tile = force_tile;
-  if (!tile) {
-    // 128x64 also when 128x128 would leave fewer than ~1.5 workgroups per CU
-    // or a half-empty last column tile (measured: 2.5 % per train step)
-    constexpr int policy = 2;  // (policies 0 / 1 measured slower: DESIGN.md §8)
-    const long b128 = (long)cdiv(M, 128) * cdiv(N, 128) * splits;
-    const long b12864 = (long)cdiv(M, 128) * cdiv(N, 64) * splits;
-    if (N <= 64 && (long)cdiv(M, 128) * splits >= 160) tile = 12864;
-    else if (policy >= 1 && N > 64 && b128 < 384 && b12864 >= 384) tile = 12864;
-    else if (policy >= 2 && N > 64 && N % 128 != 0 && N % 64 == 0 && b12864 >= 160) tile = 12864;
-    else if (N > 64 && b128 >= 160) tile = 128;
-    else tile = 64;
-  }
+  const int tile = force_tile ? force_tile : auto_tile(M, N, splits);
   const bool lean_store = ep.mode == EPI_STORE && ep.act == ACT_NONE && !ep.rowadd && !ep.resid && !ep.drop_thr &&
                           ep.drop_scale == 1.f && N % 4 == 0 && ep.ldo % 4 == 0 && ((uintptr_t)ep.out & 15) == 0;
   int ek = ep.mode == EPI_SLAB ? EK_SLAB : (lean_store ? EK_STORE : EK_GEN);

@@ -1,5 +1,6 @@
 // C-ABI conv forward (3x3 implicit GEMM, patch embedding) on the MFMA GEMM.
 #include "gemm_host.h"
+#include "gemm_conv_halo.h"
 
 // rows per BatchNorm partial tile written by hvit_conv_fwd for geometry g
 extern "C" int hvit_conv_bn_tile_rows(const hvit_conv_geom_t* g) {
@@ -53,9 +54,16 @@ extern "C" int hvit_conv_fwd(int dt, const hvit_conv_geom_t* g, const void* w_pa
     int Kt = la.Kt;
     if constexpr (sizeof(T) == 2) {
       constexpr int ft = 0;  // automatic tile (forced 128x128 / 128x64 measured slower)
-      if (conv_fast_ok(la, g->N))
+      if (conv_fast_ok(la, g->N)) {
+        // one source, no upsample, whole-row tiles: the input halo stays in LDS (gemm_conv_halo.h)
+        if (conv_halo_try(conv_fast(la, g->N), dense<T, true>(w_packed, Kt, g->Cout, Kt), la.P, g->Cout, Kt, ep,
+                          (hipStream_t)stream, true)) {
+          HVIT_LAUNCH_CHECK();
+          return HVIT_OK;
+        }
         return launch_gemm<T>(conv_fast(la, g->N), dense<T, true>(w_packed, Kt, g->Cout, Kt), la.P, g->Cout, Kt, 1,
                               ep, (hipStream_t)stream, ft);
+      }
     }
     // odd reduction length (Cin=1 first conv): weights take the scalar load path
     return launch_gemm<T>(la, dense<T, true>(w_packed, Kt, g->Cout, Kt), la.P, g->Cout, Kt, 1, ep,
@@ -63,3 +71,12 @@ extern "C" int hvit_conv_fwd(int dt, const hvit_conv_geom_t* g, const void* w_pa
   });
 }
 
+
+// the halo image's address map, for the CPU check of its slots and bank pattern
+extern "C" int hvit_conv_halo_off(int H, int W, int C, int rows, int hy, int hx, int chunk) {
+  HaloGeom hg;
+  if ((rows != 128 && rows != 256) || !halo_geom(H, W, C, rows, &hg)) return -1;
+  const int TW = 1 << hg.tws, TR = rows >> hg.tws;
+  if (hy < 0 || hy >= TR + 2 || hx < 0 || hx >= TW + 2 || chunk < 0 || chunk >= C / 8) return -1;
+  return halo_off(hy, hx, chunk, TW + 2, C);
+}

@@ -1,5 +1,6 @@
 // C-ABI conv data gradient (3x3 implicit GEMM, patch col2im) on the MFMA GEMM.
 #include "gemm_host.h"
+#include "gemm_conv_halo.h"
 
 extern "C" int hvit_conv_dgrad(int dt, const hvit_conv_geom_t* g, const void* dy, const void* w, void* dx,
                                int dx_dt, void* stream) {
@@ -45,8 +46,14 @@ extern "C" int hvit_conv_dgrad(int dt, const hvit_conv_geom_t* g, const void* dy
     auto la = conv_a<T>(g, dy, g->Cout, nullptr, 0, Ho, Wo, 1, g->KS, 1, g->pad);
     int Kt = la.Kt;
     if constexpr (sizeof(T) == 2) {
-      if (conv_fast_ok(la, g->N))
+      if (conv_fast_ok(la, g->N)) {
+        // whole-row tiles of dy: its halo stays in LDS (gemm_conv_halo.h)
+        if (conv_halo_try(conv_fast(la, g->N), dense<T, true>(w, Kt, Ctot, Kt), la.P, Ctot, Kt, ep, st, false)) {
+          HVIT_LAUNCH_CHECK();
+          return HVIT_OK;
+        }
         return launch_gemm<T>(conv_fast(la, g->N), dense<T, true>(w, Kt, Ctot, Kt), la.P, Ctot, Kt, 1, ep, st);
+      }
     }
     return launch_gemm<T>(la, dense<T, true>(w, Kt, Ctot, Kt), la.P, Ctot, Kt, 1, ep, st);
   });

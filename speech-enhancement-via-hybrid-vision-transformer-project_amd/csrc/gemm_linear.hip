@@ -1,6 +1,7 @@
 // C-ABI Linear fwd / dgrad / wgrad on the MFMA GEMM (see gemm_host.h).
 #include "gemm_host.h"
 #include "gemm_ring.h"
+#include "gemm_conv_halo.h"
 
 int hvit_attn_tune(int value);
 int hvit_fp8_tune(int value);  // attention_fp8.hip
@@ -272,6 +273,12 @@ extern "C" int hvit_gemm_tune(int what, int value) {
     if (value >= 2 && value <= 4) dma_depth_ref() = value;
     return old;
   }
+  if (what == 9) {  // 3x3 conv fwd / dgrad A operand: 0 per-tap im2col, 1 halo-resident where measured faster, 2 wherever it applies
+    const int old = conv_halo_mode_ref();
+    if (value >= 0 && value <= 2) conv_halo_mode_ref() = value;
+    return old;
+  }
+  if (what == 10) return (int)conv_halo_count_ref();  // halo-resident launches so far
   if (what == 7) return hvit_wgrad_group_tune(value);  // grouped weight gradients: 0 256x256 tiles, 1 256x128
   if (what == 4) return hvit_attn_tune(value);  // attention backward for N <= 256: 1 single pass, 0 two kernels
   if (what == 5) return hvit_fp8_tune(value);  // fp8 attention forward: 0 round-4 kernel, 1 v2 16 waves, 2 v2 8 waves
