@@ -450,9 +450,12 @@ int hvit_loss_bwd(const float* pred, const float* tgt, int B, long long P, const
 
 /* clip_grad_norm_ (training/trainer.py:170-174 -> torch.nn.utils, norm 2) and
  * AdamW (training/optimizer.py:53-61 -> torch.optim.AdamW).  Tensor lists are
- * passed by value to the kernels (40 per launch), so nothing is copied to the
- * device.  hvit_clip_coef writes out[0] = total 2-norm of all tensors,
- * out[1] = min(max_norm / (norm + 1e-6), 1); hvit_scale_tensors multiplies
+ * passed by value to the kernels (60 per AdamW launch, 128 per sum-of-squares
+ * or scale launch; longer lists take several launches), so nothing is copied
+ * to the device.  A tensor with numel 0 may have a NULL pointer.
+ * hvit_clip_coef writes out[0] = total 2-norm of all tensors,
+ * out[1] = min(max_norm / (norm + 1e-6), 1), NaN when the norm is NaN (as
+ * torch.clamp, so one NaN gradient makes every gradient NaN); hvit_scale_tensors multiplies
  * each tensor in place by coef[1] (torch's in-place clip).  hvit_adamw applies
  * one AdamW step per item, multiplying each gradient by coef[1] when coef is
  * non-NULL (clip fused into the update, gradients left untouched), and writes

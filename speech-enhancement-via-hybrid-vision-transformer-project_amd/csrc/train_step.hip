@@ -235,7 +235,8 @@ __global__ __launch_bounds__(256) void sumsq_kernel(SumsqArgs a, float* __restri
   if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
-// out[0] = total norm, out[1] = min(max_norm / (norm + 1e-6), 1)
+// out[0] = total norm, out[1] = clamp(max_norm / (norm + 1e-6), max = 1) with torch.clamp's NaN rule: a NaN
+// norm gives a NaN coefficient (fminf alone would return 1 and hide it)
 __global__ __launch_bounds__(256) void clip_finalize_kernel(const float* __restrict__ part, int n, float max_norm,
                                                            float* __restrict__ out) {
   __shared__ float red[4];
@@ -245,7 +246,8 @@ __global__ __launch_bounds__(256) void clip_finalize_kernel(const float* __restr
   if (threadIdx.x == 0) {
     const float norm = sqrtf(s);
     out[0] = norm;
-    out[1] = fminf(max_norm / (norm + 1e-6f), 1.f);
+    const float r = max_norm / (norm + 1e-6f);
+    out[1] = r != r ? r : fminf(r, 1.f);
   }
 }
 
@@ -466,7 +468,9 @@ static int fill_sumsq(SumsqArgs& a, const hvit_tensor_t* t, int base, int count,
   a.start[0] = 0;
   for (int k = 0; k < count; ++k) {
     const hvit_tensor_t& x = t[base + k];
-    HVIT_CHECK(x.ptr && x.numel >= 0, "hvit: tensor %d: null pointer or negative numel", base + k);
+    // (an empty tensor's pointer may be NULL: it has no units, so no kernel touches it)
+    HVIT_CHECK(x.numel >= 0 && (x.ptr || x.numel == 0), "hvit: tensor %d: null pointer or negative numel",
+               base + k);
     a.g[k] = (const float*)x.ptr;
     a.n[k] = (long)x.numel;
     const long units = (long)((x.numel + 3) / 4);
@@ -529,8 +533,8 @@ extern "C" int hvit_adamw_dev(int count, const hvit_adamw_item_t* items, const h
     a.start[0] = 0;
     for (int k = 0; k < a.count; ++k) {
       const hvit_adamw_item_t& it = items[base + k];
-      HVIT_CHECK(it.param && it.grad && it.exp_avg && it.exp_avg_sq && it.numel >= 0,
-                 "hvit_adamw: item %d: null pointer", base + k);
+      HVIT_CHECK(it.numel >= 0 && ((it.param && it.grad && it.exp_avg && it.exp_avg_sq) || it.numel == 0),
+                 "hvit_adamw: item %d: null pointer", base + k);  // (an empty item's pointers may be NULL)
       HVIT_CHECK(aligned16(it.param) && aligned16(it.grad) && aligned16(it.exp_avg) && aligned16(it.exp_avg_sq) &&
                      (!it.shadow_bf16 || (((uintptr_t)it.shadow_bf16) & 7) == 0),
                  "hvit_adamw: item %d: alignment (16 B; shadow 8 B)", base + k);

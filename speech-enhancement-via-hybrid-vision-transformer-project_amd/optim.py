@@ -48,7 +48,8 @@ def _refs(tensors) -> "L.TensorRef * n":
 
 
 def _clip_coef(grads, max_norm: float) -> torch.Tensor:
-    """[norm, min(max_norm / (norm + 1e-6), 1)] on the device."""
+    """[norm, min(max_norm / (norm + 1e-6), 1)] on the device (a NaN norm gives a
+    NaN coefficient, as torch.clamp does)."""
     dev = grads[0].device
     out = torch.empty(2, dtype=torch.float32, device=dev)
     ws_n = L.lib().hvit_clip_ws_elems(len(grads))
