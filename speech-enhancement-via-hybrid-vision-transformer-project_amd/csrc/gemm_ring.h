@@ -21,7 +21,13 @@
 // thread, 16-byte stores): plain (+bias, bf16 or f32, optional column sums),
 // fc1's GELU_DUAL, the residual adds of proj / fc2, fc2's GELU backward (+bias
 // grad column sums), and split-K partial slabs.  Every tile is interior (the
-// host guarantees M % BM == N % BN == 0, K slices multiples of 64).
+// host guarantees M % BM == N % BN == 0, K slices multiples of 64).  The
+// staging, each kind's arithmetic, the packed stores, the column-sum rows and
+// the split-K ticket step are gemm_epilogue.h's one definition, shared with
+// gemm_kernel; what this kernel keeps to itself is where its side operands are
+// loaded (per 64-row pass, before the staging barrier; gemm_kernel prefetches
+// h before its K loop and loads the residual after the barrier) and that an
+// f32 h is rounded to bf16 on the way in (gemm_kernel hands in the exact f32).
 #pragma once
 #include "gemm.h"
 
@@ -174,22 +180,6 @@ struct RingCore {
   }
 };
 
-// wide epilogue helpers ------------------------------------------------------
-__device__ __forceinline__ u32x4 pack8(const f32x4& a, const f32x4& b) {
-  u32x4 u;
-  u[0] = f2bf2(a[0], a[1]);
-  u[1] = f2bf2(a[2], a[3]);
-  u[2] = f2bf2(b[0], b[1]);
-  u[3] = f2bf2(b[2], b[3]);
-  return u;
-}
-__device__ __forceinline__ void unpack8(const u32x4& u, f32x4& a, f32x4& b) {
-  a = (f32x4){__uint_as_float(u[0] << 16), __uint_as_float(u[0] & 0xffff0000u), __uint_as_float(u[1] << 16),
-              __uint_as_float(u[1] & 0xffff0000u)};
-  b = (f32x4){__uint_as_float(u[2] << 16), __uint_as_float(u[2] & 0xffff0000u), __uint_as_float(u[3] << 16),
-              __uint_as_float(u[3] & 0xffff0000u)};
-}
-
 // EK: EK_STORE (+bias, out bf16 / f32, colsum), EK_GELU_DUAL, EK_RESID,
 // EK_GELU_BWD (+colsum), EK_SLAB (f32 split-K partial, slab z = blockIdx's K slice)
 template <int BM, int BN, int WM, int WN, int NB, bool KCA, bool KCB, int EK>
@@ -211,7 +201,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NB == 2) ? (BN == 64
   const int m0 = t3.mt * BM, n0 = t3.nt * BN;
   const int kbeg = t3.z * kps;
   const int kend = min(K, kbeg + kps);
-  const int frow = lane & 15, fq = lane >> 4;
 
   f32x4 acc[FM][FN];
 #pragma unroll
@@ -236,20 +225,13 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NB == 2) ? (BN == 64
 #pragma unroll
   for (int hh = 0; hh < BM / 64; ++hh) {
     if (hh > 0) epi_barrier();
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = wm * WTM + i * 16 + fq * 4 + r - hh * 64;
-          if (row >= 0 && row < 64) Cs[row * CP + wn * WTN + j * 16 + frow] = acc[i][j][r];
-        }
+    epi_stage<CP>(Cs, acc, hh, wm, wn, lane);
     const int mbase = m0 + hh * 64;
     // this pass's side inputs, issued before the barrier so their latency
-    // overlaps it (loads cannot move above the stores that follow them)
+    // overlaps it (loads cannot move above the stores that follow them); h stays
+    // packed until its row
     u32x4 hin[NR8];
-    f32x4 ra[NR8], rb[NR8];
+    f32x4 sa[NR8], sb[NR8];
     float rsc[NR8];
     if constexpr (EK == EK_GELU_BWD) {
 #pragma unroll
@@ -268,8 +250,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NB == 2) ? (BN == 64
 #pragma unroll
       for (int i = 0; i < NR8; ++i) {
         const int m = mbase + q0 + i * RS8;
-        ra[i] = *(const f32x4*)(ep.resid + (long)m * ep.ldr + n8);
-        rb[i] = *(const f32x4*)(ep.resid + (long)m * ep.ldr + n8 + 4);
+        sa[i] = *(const f32x4*)(ep.resid + (long)m * ep.ldr + n8);
+        sb[i] = *(const f32x4*)(ep.resid + (long)m * ep.ldr + n8 + 4);
         rsc[i] = ep.rowscale ? ep.rowscale[m / ep.rows_per_sample] : 1.f;
       }
     }
@@ -278,98 +260,24 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NB == 2) ? (BN == 64
     for (int i = 0; i < NR8; ++i) {
       const int row = q0 + i * RS8;
       const int m = mbase + row;
-      f32x4 va = *(const f32x4*)(Cs + row * CP + c8 * 8);
-      f32x4 vb = *(const f32x4*)(Cs + row * CP + c8 * 8 + 4);
+      const float* crow = Cs + row * CP + c8 * 8;
       if constexpr (EK == EK_SLAB) {
         float* slab = (float*)ep.out + (long)t3.z * ep.slab_stride + (long)m * ep.ldo + n8;
-        *(f32x4*)slab = va;
-        *(f32x4*)(slab + 4) = vb;
-        continue;
-      }
-      va += b8a;
-      vb += b8b;
-      if constexpr (EK == EK_GELU_DUAL) {
-        f32x4 ka = {1.f, 1.f, 1.f, 1.f}, kb = ka;
-        if (ep.drop_thr) {
-          ka = keep4(ep, dkey, m, n8, N);
-          kb = keep4(ep, dkey, m, n8 + 4, N);
-        }
-        f32x4 ga, gb, da, db;
-        gelu_gg4(va, ga, da);
-        gelu_gg4(vb, gb, db);
-        ga *= ka;
-        gb *= kb;
-        if (ep.gd == 2) {  // GELU_DUAL_DK: the backward's multiplier carries the mask
-          da *= ka;
-          db *= kb;
-        }
-        // (no out: the inference form, HVIT_ACT_GELU -- only gelu(v) is stored)
-        if (ep.out) *(u32x4*)((bf16_t*)ep.out + (long)m * ep.ldo + n8) = ep.gd ? pack8(da, db) : pack8(va, vb);
-        *(u32x4*)((bf16_t*)ep.out2 + (long)m * ep.ldo2 + n8) = pack8(ga, gb);
-        continue;
-      }
-      if (EK != EK_STORE && ep.drop_thr) {
-        va *= keep4(ep, dkey, m, n8, N);
-        vb *= keep4(ep, dkey, m, n8 + 4, N);
-      }
-      if constexpr (EK == EK_GELU_BWD) {
-        f32x4 ha, hb;
-        unpack8(hin[i], ha, hb);
-        if (ep.gd) {
-          va *= ha;
-          vb *= hb;
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            va[e] *= gelu_grad(ha[e]);
-            vb[e] *= gelu_grad(hb[e]);
-          }
-        }
-      }
-      if constexpr (EK == EK_RESID) {
-        va = ra[i] + rsc[i] * va;
-        vb = rb[i] + rsc[i] * vb;
-      }
-      if (ep.out_dt == HVIT_BF16) {
-        *(u32x4*)((bf16_t*)ep.out + (long)m * ep.ldo + n8) = pack8(va, vb);
+        *(f32x4*)slab = *(const f32x4*)crow;
+        *(f32x4*)(slab + 4) = *(const f32x4*)(crow + 4);
       } else {
-        *(f32x4*)((float*)ep.out + (long)m * ep.ldo + n8) = va;
-        *(f32x4*)((float*)ep.out + (long)m * ep.ldo + n8 + 4) = vb;
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        cs8[e] += va[e];
-        cs8[4 + e] += vb[e];
+        if constexpr (EK == EK_GELU_BWD) unpack8(hin[i], sa[i], sb[i]);
+        epi_wide_row<EK>(ep, dkey, crow, m, n8, N, b8a, b8b, sa[i], sb[i], EK == EK_RESID ? rsc[i] : 1.f, cs8);
       }
     }
   }
   if constexpr (EK == EK_SLAB) {
-    // In-kernel split-K reduction (cdna_hip_programming.md section 5, "In-launch
-    // split-K reduction", counter form): every slice publishes its slab (plain
-    // stores, each wave's vmcnt(0), barrier, one agent release), then takes a
-    // ticket; the slice that draws splits-1 acquires and sums all slabs of the
-    // tile into red_out.  Correct for any placement of the slices; no slice
-    // waits on another, so no co-residency is assumed.  The reducer resets the
-    // ticket for the next call (tickets start zeroed: the caller's zero pool).
+    // In-kernel split-K reduction: the slice that arrives last at its tile's
+    // ticket sums all of the tile's slabs into red_out (splitk_last_arriver)
     if (ep.tickets) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      int* flag = (int*)(smem + 64 * CP * 4);  // inside the one LDS array (no second __shared__ object)
       const int splits = gridDim.z;
-      const int tile = t3.mt * gridDim.y + t3.nt;
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned prev = __hip_atomic_fetch_add(ep.tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = prev == (unsigned)(splits - 1);
-        if (last) __hip_atomic_store(ep.tickets + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *flag = last;
-      }
-      __syncthreads();
-      if (!*flag) return;
-      if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
+      // (the flag inside the one LDS array: no second __shared__ object)
+      if (!splitk_last_arriver(ep.tickets + t3.mt * gridDim.y + t3.nt, splits, (int*)(smem + 64 * CP * 4))) return;
       constexpr int RPT = BM / RS8;  // rows per thread over the whole tile
 #pragma unroll 2
       for (int i = 0; i < RPT; ++i) {
@@ -388,31 +296,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NB == 2) ? (BN == 64
     }
     return;
   }
-  if (EK != EK_GELU_DUAL && ep.colsum) {
-    float* red = Cs + 64 * CP;  // [RS8][BN]
-    epi_barrier();
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[q0 * BN + c8 * 8 + e] = cs8[e];
-    epi_barrier();
-    if (q0 == 0) {
-      // deterministic partial row m0/64 (zeros in the tile's other 64-row rows)
-      float t8[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float t = 0.f;
-        for (int k = 0; k < RS8; ++k) t += red[k * BN + c8 * 8 + e];
-        t8[e] = t;
-      }
-      float* row = ep.colsum + (long)(m0 / 64) * N + n8;
-      *(f32x4*)row = (f32x4){t8[0], t8[1], t8[2], t8[3]};
-      *(f32x4*)(row + 4) = (f32x4){t8[4], t8[5], t8[6], t8[7]};
-#pragma unroll
-      for (int r = 1; r < BM / 64; ++r) {
-        *(f32x4*)(row + (long)r * N) = (f32x4){0.f, 0.f, 0.f, 0.f};
-        *(f32x4*)(row + (long)r * N + 4) = (f32x4){0.f, 0.f, 0.f, 0.f};
-      }
-    }
-  }
+  if (EK != EK_GELU_DUAL && ep.colsum) epi_colsum8<BM, BN, RS8>(ep.colsum, Cs + 64 * CP, cs8, q0, c8, m0, n8, N);
   GEMM_STAMP(2);
 }
 

@@ -227,7 +227,6 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void wgrad_group_kernel(Table tb) 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid / WN, wn = wid % WN;
-  const int frow = lane & 15, fq = lane >> 4;
   const int c8 = tid % C8, q0 = tid / C8;
   float* Cs = (float*)smem;
   Epi none;  // (no side job)
@@ -256,15 +255,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void wgrad_group_kernel(Table tb) 
 #pragma unroll
     for (int hh = 0; hh < BM / 64; ++hh) {
       if (hh > 0) epi_barrier();
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int jj = 0; jj < FN; ++jj)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int row = wm * WTM + i * 16 + fq * 4 + r - hh * 64;
-            if (row >= 0 && row < 64) Cs[row * CP + wn * WTN + jj * 16 + frow] = acc[i][jj][r];
-          }
+      epi_stage<CP>(Cs, acc, hh, wm, wn, lane);
       epi_barrier();
 #pragma unroll
       for (int i = 0; i < NR8; ++i) {
@@ -276,25 +267,10 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void wgrad_group_kernel(Table tb) 
     }
     if (!pb) return;
     // publish the slab, take a ticket; the last piece to arrive sums all of the
-    // tile's slabs in piece order (cdna_hip_programming.md, in-launch split-K
-    // reduction, counter form: no piece waits for another, no co-residency)
+    // tile's slabs in piece order (gemm_epilogue.h, splitk_last_arriver: no piece
+    // waits for another, no co-residency)
     const int rt = w / tb.s;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* flag = (int*)(smem + 64 * CP * 4);
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned prev = __hip_atomic_fetch_add(tb.tickets + rt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = prev == (unsigned)(tb.s - 1);
-      if (last) __hip_atomic_store(tb.tickets + rt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *flag = last;
-    }
-    __syncthreads();
-    if (!*flag) return;
-    if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    if (!splitk_last_arriver(tb.tickets + rt, tb.s, (int*)(smem + 64 * CP * 4))) return;
     const float* s0 = tb.slabs + (long)(rt * tb.s) * (BM * 256);
     float* dw = pr.dw + (long)m0 * pr.k_in + n0;
 #pragma unroll 2
