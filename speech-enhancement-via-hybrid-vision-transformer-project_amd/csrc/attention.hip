@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "attention_tile.h"
 #include "common.h"
 
 namespace hvit {
@@ -473,107 +474,10 @@ __global__ __launch_bounds__(AT_THREADS) void mhsa_dkv_kernel(const T* __restric
 }
 
 // ============================================================================
-// v2 fast path: bf16, head_dim 64, N <= 256 keys (the HybridViT shapes).
-//
-// The whole K and V (or Q and dO) of one (b, h) live in LDS as row-major
-// [row][64] bf16 images (128-B rows, 16-B chunks XOR-swizzled by row & 7), so
-// every tile is staged once per workgroup with plain 16-byte copies -- no
-// transposed staging.  Scores are computed TRANSPOSED (S^T = K Q^T): the
-// 16x16 MFMA accumulator then holds, per lane, 4 consecutive keys of one
-// query, which is exactly the B-operand layout of v_mfma_f32_16x16x16_bf16,
-// so P^T (and dS^T) feed the next MFMA straight from registers; the other
-// operand (V^T, K^T, dO^T, Q^T) is read with ds_read_b64_tr_b16.  A lane's 4
-// keys also form one dropout-hash group (one 64-bit hash per 16x16 tile).
+// v2 fast path: bf16, head_dim 64, N <= 512 keys (the HybridViT shapes).  The
+// LDS images, fragment reads, keep-bit layout and tile pieces: attention_tile.h.
 // ============================================================================
 constexpr int V2_KMAX = 512;  // the largest token count of the register-resident kernels
-constexpr int V2_ROWB = 128;  // bytes per 64-element bf16 row
-typedef short v4s_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s_t lds_v4s_t;
-
-__device__ __forceinline__ int v2_off(int row, int chunk) { return row * V2_ROWB + ((chunk ^ (row & 7)) << 4); }
-
-// Same image filled by LDS-DMA (global_load_lds_dwordx4): no registers, no
-// per-chunk load->store latency chain.  One wave-instruction writes 1 KiB =
-// 8 rows; the destination is lane-linear, so the XOR swizzle moves to the
-// source address (lane L fetches logical chunk (L%8) ^ row&7 of row 8p + L/8).
-// Rows >= n re-read row n-1 (finite data; every use of those rows is masked or
-// multiplied by an exact zero).  `rows` is a multiple of 8.
-template <int WAVES>
-__device__ __forceinline__ void v2_stage_glds(char* dst, const bf16_t* src, long pitch, int n, int rows) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int rl = lane >> 3, cp = lane & 7;
-  for (int pc = w; pc < (rows >> 3); pc += WAVES) {
-    const int row = pc * 8 + rl;
-    const int srow = row < n ? row : n - 1;
-    const bf16_t* g = src + (long)srow * pitch + ((cp ^ rl) << 3);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)(dst + pc * 1024), 16, 0, 0);
-  }
-}
-// 16x16x32 operand fragment: row `row`, k = 32*s + 8*fq .. +7
-__device__ __forceinline__ u32x4 v2_frag(const char* img, int row, int s, int fq) {
-  return *(const u32x4*)(img + v2_off(row, 4 * s + fq));
-}
-// transposed 4-row read: lane (g = lane>>4, i = lane&15) receives
-// img[k0 + 4g + 0..3][c0 + i]  (k0 multiple of 16, c0 multiple of 16)
-__device__ __forceinline__ v4s_t v2_tr(const char* img, int k0, int c0, int lane) {
-  const int g = lane >> 4, li = lane & 15;
-  const int row = k0 + 4 * g + (li >> 2);
-  const int col = c0 + 4 * (li & 3);
-  const char* a = img + row * V2_ROWB + (((col >> 3) ^ (row & 7)) << 4) + (col & 7) * 2;
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)a);
-}
-// Per-lane constant parts of the two read patterns (row = 16*j + lane part,
-// and row & 7 depends on the lane part only), so a tile read is one LDS
-// instruction at base + 2048*j + const.
-struct V2Lane {
-  int kc[2];  // v2_frag offsets for s = 0, 1 (row = frow)
-  int tr[4];  // v2_tr offsets for column block t = 0..3 (rows 4g + li/4)
-  __device__ __forceinline__ V2Lane(int lane) {
-    const int frow = lane & 15, fq = lane >> 4;
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) kc[s2] = frow * V2_ROWB + (((4 * s2 + fq) ^ (frow & 7)) << 4);
-    const int r0 = 4 * fq + (frow >> 2), cb = (frow & 3) >> 1, inner = (frow & 1) * 8;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) tr[t] = r0 * V2_ROWB + (((2 * t + cb) ^ (r0 & 7)) << 4) + inner;
-  }
-};
-__device__ __forceinline__ u32x4 v2_fragj(const char* img, const V2Lane& L, int j, int s2) {
-  return *(const u32x4*)(img + j * 16 * V2_ROWB + L.kc[s2]);
-}
-__device__ __forceinline__ v4s_t v2_trj(const char* img, const V2Lane& L, int j, int t) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)(img + j * 16 * V2_ROWB + L.tr[t]));
-}
-__device__ __forceinline__ f32x4 v2_mma32(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(s16x8, a), __builtin_bit_cast(s16x8, b), c, 0,
-                                                 0, 0);
-}
-// Score tile straight from its MFMAs into a branch (the partial-tile mask):
-// hipcc pads the MFMA -> VALU-read distance on the fall-through edge but not
-// on the taken one (1-3 wait states in the .s where an 8-pass XDL result needs
-// 11), so the wait goes inside a statement that takes the tile as an operand.
-__device__ __forceinline__ void v2_settle(f32x4& a) { asm volatile("s_nop 7\n\ts_nop 3" : "+v"(a)); }
-// 16x16x32 operand from two transposed 4-row reads (tiles jj and jj + 1):
-// k = 8g + e  <->  row 16*(jj + e/4) + 4g + e%4
-__device__ __forceinline__ u32x4 v2_cat(v4s_t lo, v4s_t hi) {
-  const uint2 a = __builtin_bit_cast(uint2, lo), b = __builtin_bit_cast(uint2, hi);
-  return (u32x4){a.x, a.y, b.x, b.y};
-}
-__device__ __forceinline__ u32x4 v2_trj2(const char* img, const V2Lane& L, int jj, int t) {
-  return v2_cat(v2_trj(img, L, jj, t), v2_trj(img, L, jj + 1, t));
-}
-__device__ __forceinline__ v4s_t v2_pack(f32x4 v) {
-  uint2 u;
-  u.x = f2bf2(v[0], v[1]);
-  u.y = f2bf2(v[2], v[3]);
-  return __builtin_bit_cast(v4s_t, u);
-}
-// dropout multipliers of 4 consecutive keys kj..kj+3 (kj % 4 == 0) of query qi
-__device__ __forceinline__ f32x4 v2_keep(uint64_t bh, int N, int qi, int kj, uint32_t thr, float dscale,
-                                         unsigned long long seed, uint32_t site) {
-  const uint64_t idx = (bh * N + qi) * (uint64_t)N + kj;
-  return keep4_at(rng_key(seed, site), idx, thr, dscale);
-}
 
 // forward: workgroup = (b, h, 16*WAVES queries); wave = 16 queries x all keys.
 // WAVES = 16 covers all N <= 256 queries of a (b, h) in one workgroup, so K
@@ -643,6 +547,12 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_v2(const bf16_t* __restri
         a = v2_mma32(v2_fragj(Kc, LN, j, 0), qf[0], a);
         a = v2_mma32(v2_fragj(Kc, LN, j, 1), qf[1], a);
         v2_settle(a);
+        // (this kernel's own partial-tile mask: inlined from a shared v2_mask_max, hipcc
+        // lays the branch out differently and the partial-tile forms grow,
+        // 2093 -> 2131 and 3957 -> 4084 instructions, N = 496 forward 67.4 ->
+        // 67.7 us.  In that layout hipcc pads the taken edge itself: whether the
+        // MFMA -> VALU hazard shows depends on code layout, which is why
+        // v2_settle stays whatever this branch compiles to.)
         if (!FULL && c0 + 16 * j + 16 > N) {  // wave-uniform: only a partial last tile
 #pragma unroll
           for (int r = 0; r < 4; ++r)
@@ -686,8 +596,7 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_v2(const bf16_t* __restri
     // 2jp, 2jp + 1 (keys c0 + 16(2jp + e/4) + 4fq + e%4), the A operand the
     // matching transposed reads of V.  A missing odd tile is P = 0 against
     // staged (finite) V rows.
-    // keep bits for the backward (kbits non-null): bit 8*jp + 4*e + r of this
-    // lane's word pair of chunk c0/256 = keep(q, key c0 + 32*jp + 16*e + 4*fq + r)
+    // this lane's keep-bit word pair of chunk c0/256 for the backward (kbits non-null)
     uint32_t kb[2] = {0u, 0u};
 #pragma unroll
     for (int jp = 0; jp < CH / 32; ++jp) {
@@ -695,25 +604,18 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_v2(const bf16_t* __restri
         f32x4 p0 = st[2 * jp];
         f32x4 p1 = (2 * jp + 1 < nkt) ? st[2 * jp + 1] : (f32x4){0.f, 0.f, 0.f, 0.f};
         if (thr) {
-          uint32_t b8 = 0u;
+          uint32_t b8 = 0u;  // the pair's two nibbles
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
-            if (2 * jp + e < nkt) {
-              // rng_pair(rk, qrow + c0 + 32jp + 16e + 4fq) and (.. + 2) in 32 bits:
+            const int j = 2 * jp + e;
+            if (j < nkt) {
+              // rng_pair(rk, qrow + c0 + 16j + 4fq) and (.. + 2) in 32 bits:
               // qrow and the offset are even, so (qrow + off) >> 1 = qrow / 2 + off / 2
-              const uint32_t x0 = hq + (uint32_t)(c0 / 2 + 16 * jp + 8 * e);
-              const uint32_t h0 = hash32(rk ^ x0), h1 = hash32(rk ^ (x0 + 1u));
-              const bool k0 = (h0 & 0xffffu) >= thr, k1 = (h0 >> 16) >= thr;
-              const bool k2 = (h1 & 0xffffu) >= thr, k3 = (h1 >> 16) >= thr;
-              f32x4& pp = e ? p1 : p0;
-              pp[0] = k0 ? pp[0] : 0.f;
-              pp[1] = k1 ? pp[1] : 0.f;
-              pp[2] = k2 ? pp[2] : 0.f;
-              pp[3] = k3 ? pp[3] : 0.f;
-              b8 |= ((uint32_t)k0 | ((uint32_t)k1 << 1) | ((uint32_t)k2 << 2) | ((uint32_t)k3 << 3)) << (4 * e);
+              const uint32_t nib = v2_keep_step(rk, hq + (uint32_t)(c0 / 2 + 8 * j), thr, e ? p1 : p0);
+              b8 |= nib << (kb_nibble(j) - kb_nibble(2 * jp));
             }
           }
-          kb[jp >> 2] |= b8 << (8 * (jp & 3));
+          kb[kb_nibble(2 * jp) >> 5] |= b8 << (kb_nibble(2 * jp) & 31);
         }
         const u32x4 pb = v2_cat(v2_pack(p0), v2_pack(p1));
 #pragma unroll
@@ -721,7 +623,7 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_v2(const bf16_t* __restri
       }
     }
     if (qin && kbits && thr)
-      *(uint2*)(kbits + (((uint64_t)(c0 / CH) * BHN + bh * N + q) * 4 + fq) * 2) = make_uint2(kb[0], kb[1]);
+      *(uint2*)(kbits + kb_pair(c0 / CH, BHN, bh * N, q, fq)) = make_uint2(kb[0], kb[1]);
   };
   chunk(std::integral_constant<int, 0>());
   if constexpr (KMAX > CH) {
@@ -730,49 +632,8 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_v2(const bf16_t* __restri
   if (qin) {
     const float inv = 1.f / sum;
     const float os = thr ? inv * dscale : inv;
-    bf16_t* op = o + ((long)b * N + q) * D + h * 64;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      uint2 u;
-      u.x = f2bf2(ot[t][0] * os, ot[t][1] * os);
-      u.y = f2bf2(ot[t][2] * os, ot[t][3] * os);
-      *(uint2*)(op + 16 * t + 4 * fq) = u;
-    }
+    v2_store_row(o + ((long)b * N + q) * D + h * 64, ot, os, fq);
     if (fq == 0) lse[bh * N + q] = (mxc + log2f(sum)) * 0.6931471805599453f;
-  }
-}
-
-// Column sums over a workgroup's rows of one head's [rows][64] gradient block
-// held as acc[t][r] (column d = 16t + 4fq + r, row = the lane's query / key):
-// the 16 lanes of a quarter (frow) by xor shuffles, the waves through LDS `red`
-// ([WAVES][64] f32), then one plain store per column into out[0..63] (this
-// workgroup's partial of the qkv bias gradient, attention.py:55; a later pass
-// sums the partials: 32 workgroups adding to one address serialised at L2
-// and cost more than the reduction pass they replaced).
-template <int WAVES>
-__device__ __forceinline__ void v2_colsum64(const f32x4 (&acc)[4], float mul, float* red, float* out) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int frow = lane & 15, fq = lane >> 4;
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      // the 16 rows of a quarter are one DPP row: rotate-and-add (row_ror 8,
-      // 4, 2, 1) leaves the row sum in every lane, on the VALU (no LDS
-      // permutes)
-      float v = acc[t][r] * mul;
-      v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));
-      v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));
-      v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false));
-      v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));
-      if (frow == 0) red[w * 64 + 16 * t + 4 * fq + r] = v;
-    }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < WAVES; ++i) s += red[i * 64 + threadIdx.x];
-    out[threadIdx.x] = s;
   }
 }
 
@@ -811,6 +672,8 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_dq_v2(const bf16_t* __restric
     if (qv) {
       qf[s2] = *(const u32x4*)(base + (long)q * pitch + 32 * s2 + 8 * fq);
       df[s2] = *(const u32x4*)(dout + ((long)b * N + q) * D + h * 64 + 32 * s2 + 8 * fq);
+      // (this kernel's own copy of v2_dot8: with the shared one it grew 1096 -> 1100 and
+      // 1130 -> 1137 instructions and the N = 496 backward left the earlier version's range)
       const u32x4 of = *(const u32x4*)(o + ((long)b * N + q) * D + h * 64 + 32 * s2 + 8 * fq);
 #pragma unroll
       for (int e = 0; e < 4; ++e)
@@ -830,7 +693,7 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_dq_v2(const bf16_t* __restric
     kb64[c] = 0ull;
     if (kbits && thr && qv && 256 * c < N) {
       const uint64_t BHN = (uint64_t)gridDim.z * H * N;
-      const uint2 w2 = *(const uint2*)(kbits + (((uint64_t)c * BHN + bh * N + q) * 4 + fq) * 2);
+      const uint2 w2 = *(const uint2*)(kbits + kb_pair(c, BHN, bh * N, q, fq));
       kb64[c] = (unsigned long long)w2.x | ((unsigned long long)w2.y << 32);
     }
   }
@@ -857,7 +720,7 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_dq_v2(const bf16_t* __restric
       f32x4 keep = {1.f, 1.f, 1.f, 1.f};
       if (thr && kbits) {
         const unsigned long long kw = (KMAX > 256 && (j >> 4)) ? kb64[KMAX / 256 - 1] : kb64[0];
-        const uint32_t b4 = (uint32_t)(kw >> (8 * ((j & 15) >> 1) + 4 * (j & 1))) & 0xFu;
+        const uint32_t b4 = (uint32_t)(kw >> kb_nibble(j)) & 0xFu;
 #pragma unroll
         for (int r = 0; r < 4; ++r) keep[r] = (b4 >> r) & 1u ? dscale : 0.f;
       } else if (thr) {
@@ -880,16 +743,7 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_dq_v2(const bf16_t* __restric
 #pragma unroll
     for (int t = 0; t < 4; ++t) dq[t] = v2_mma32(v2_trj2(Ks, LN, j0, t), db, dq[t]);
   }
-  if (qv) {
-    bf16_t* dp_out = dqkv + ((long)b * N + q) * pitch + h * 64;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      uint2 u;
-      u.x = f2bf2(dq[t][0] * scale, dq[t][1] * scale);
-      u.y = f2bf2(dq[t][2] * scale, dq[t][3] * scale);
-      *(uint2*)(dp_out + 16 * t + 4 * fq) = u;
-    }
-  }
+  if (qv) v2_store_row(dqkv + ((long)b * N + q) * pitch + h * 64, dq, scale, fq);
   // q bias gradient (queries >= N hold dq = 0)
   if (dbias)
     v2_colsum64<WAVES>(dq, scale, (float*)(smem + 2 * KMAX * V2_ROWB),
@@ -947,17 +801,9 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_dkv_v2(const bf16_t* __restri
   }
   const bool use_kb = kbits && thr;
   const int kchunk = (blockIdx.x * WAVES * 16) >> 8;  // the 256-key chunk of this workgroup's keys
-  if (use_kb)
-    for (int i = threadIdx.x; i < N * 2; i += WAVES * 64) {
-      const u32x4 v = ((const u32x4*)(kbits + ((uint64_t)kchunk * gridDim.z * H * N + bh * N) * 8))[i];
-      const int q = i >> 1, w0 = 4 * (i & 1);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) Kb[(w0 + e) * KBP + q] = v[e];
-    }
-  // this lane's key inside a query's bit pair (chunk-relative key kl): word fq' * 2 + half, bit position
-  const int kl = key & 255;
-  const int kbit = 8 * (kl >> 5) + 4 * ((kl >> 4) & 1) + (kl & 3);
-  const int kword = ((kl >> 2) & 3) * 2 + (kbit >> 5), kshift = kbit & 31;
+  if (use_kb) kb_stage_t<WAVES * 64>(Kb, KBP, kbits + kb_pair(kchunk, (uint64_t)gridDim.z * H * N, bh * N, 0, 0), N);
+  // this lane's key in the staged bits
+  const int kword = kb_word(key & 255), kshift = kb_shift(key & 255);
   __syncthreads();
   const float c2 = scale * 1.4426950408889634f;
   // accumulators: rows = d (16t + 4fq + r), column = this lane's key
@@ -976,6 +822,10 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_dkv_v2(const bf16_t* __restri
       s = v2_mma32(v2_fragj(Qs, LN, j, 1), kf[1], s);
       dp = v2_mma32(v2_fragj(Ds, LN, j, 0), vf[0], dp);
       dp = v2_mma32(v2_fragj(Ds, LN, j, 1), vf[1], dp);
+      // This kernel's own copy of the key-major tile, its dropout form chosen at run
+      // time (thr, use_kb): through the shared tile the N = 496 backward measured
+      // 116.3 -> 117.1 us with keep bits and 140.5 -> 142.2 us re-hashed, outside
+      // the hand-copied version's run-to-run range (114 -> 118 VGPRs).
       // dropout: lane (quad position c = key & 3) hashes query row 16j+4fq+c of
       // its key group (two pair hashes); the quad exchanges the 16-bit slices
       // (4 queries x 4 keys)
@@ -1004,7 +854,6 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_dkv_v2(const bf16_t* __restri
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int qi = 16 * j + 4 * fq + r;
         float kp = 1.f;
         if (use_kb) {
           kp = ((kw4[r] >> kshift) & 1u) ? dscale : 0.f;  // (rows >= N: p is 0 there)
@@ -1031,6 +880,8 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_dkv_v2(const bf16_t* __restri
   }
   if (kv) {
     bf16_t* row = dqkv + ((long)b * N + key) * pitch + h * 64;
+    // (dK and dV stores interleaved as before the shared v2_store_row: kept with this
+    // kernel's own tile above, the two were not timed apart)
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       uint2 u;
@@ -1083,8 +934,9 @@ __device__ __forceinline__ int fb_acc(int q, int c) { return q * 256 + ((c ^ (q 
 // units XOR-swizzled by row & 7
 __device__ __forceinline__ int fb_scr(int row, int unit) { return row * 64 + ((unit ^ (row & 7)) << 3); }
 
-// FULL: N == 256 (no row / tile range tests).  DM: the dropout form, 0 none,
-// 1 the forward's keep bits, 2 re-hashed (mhsa_dkv_v2's quad exchange).
+// FULL: N == 256 (no row / tile range tests).  DM: the dropout form,
+// V2_KEEP_NONE, V2_KEEP_BITS (the forward's keep bits) or V2_KEEP_HASH
+// (re-hashed, mhsa_dkv_v2's quad exchange).
 template <bool FULL, int DM>
 __global__ __launch_bounds__(FB_WAVES * 64) void mhsa_bwd_fused(
     const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o, const bf16_t* __restrict__ dout,
@@ -1139,34 +991,19 @@ __global__ __launch_bounds__(FB_WAVES * 64) void mhsa_bwd_fused(
     orow[c] = qdv ? *(const u32x4*)(o + ((long)b * N + qd) * D + h * 64 + 32 * hf + 8 * c) : (u32x4){0u, 0u, 0u, 0u};
   const float lq = (qdv && hf == 0) ? lse[bh * N + qd] * 1.4426950408889634f : 0.f;
   // the forward's keep bits of this (b, h), transposed: Kb[word][query] (mhsa_dkv_v2's layout)
-  constexpr bool use_kb = DM == 1;
-  if (use_kb)
-    for (int i = threadIdx.x; i < N * 2; i += FB_WAVES * 64) {
-      const u32x4 v = ((const u32x4*)(kbits + bh * N * 8))[i];
-      const int q = i >> 1, w0 = 4 * (i & 1);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) Kb[(w0 + e) * FB_KBP + q] = v[e];
-    }
-  int kword[2], kshift[2];
+  if (DM == V2_KEEP_BITS) kb_stage_t<FB_WAVES * 64>(Kb, FB_KBP, kbits + kb_pair(0, 0, bh * N, 0, 0), N);
+  int kword[2], kshift[2];  // this wave's two keys in the staged bits
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {
-    const int kl = 32 * w + 16 * kt + frow;
-    const int kbit = 8 * (kl >> 5) + 4 * ((kl >> 4) & 1) + (kl & 3);
-    kword[kt] = ((kl >> 2) & 3) * 2 + (kbit >> 5);
-    kshift[kt] = kbit & 31;
+    kword[kt] = kb_word(32 * w + 16 * kt + frow);
+    kshift[kt] = kb_shift(32 * w + 16 * kt + frow);
   }
   __syncthreads();
   {
     float dl = 0.f;
     if (qdv) {
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const u32x4 x = *(const u32x4*)(Ds + v2_off(qd, 4 * hf + c)), y = orow[c];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          dl += __uint_as_float(x[e] << 16) * __uint_as_float(y[e] << 16) +
-                __uint_as_float(x[e] & 0xffff0000u) * __uint_as_float(y[e] & 0xffff0000u);
-      }
+      for (int c = 0; c < 4; ++c) dl = v2_dot8(dl, *(const u32x4*)(Ds + v2_off(qd, 4 * hf + c)), orow[c]);
     }
     dl += __shfl_xor(dl, 1, 64);
     if (hf == 0) {  // (read in the step loop, after the barriers below)
@@ -1222,40 +1059,32 @@ __global__ __launch_bounds__(FB_WAVES * 64) void mhsa_bwd_fused(
             dp = v2_mma32(da0, vf[kt][0], dp);
             dp = v2_mma32(da1, vf[kt][1], dp);
             const int key = 32 * w + 16 * kt + frow;
-            uint32_t hlo = 0u, hhi = 0u;
-            if (DM == 2) {  // re-hash (mhsa_dkv_v2's quad exchange)
+            if constexpr (DM != V2_KEEP_HASH) {
+              v2_bwd_tile_km<FULL, DM>(sv, dp, l4, d4, c2, j, N, FULL || kv[kt], Kb + kword[kt] * FB_KBP, kshift[kt],
+                                       dscale, pd[bq][kt], dsv[bq][kt]);
+            } else {
+              // The re-hash form's own copy of the tile (mhsa_dkv_v2's quad exchange): through
+              // v2_bwd_tile_km the N = 256 re-hash backward measured 34.7 -> 35.2 us
+              // (2158 -> 2164 instructions), outside the earlier version's range.
               const int qc = 16 * j + 4 * fq + (frow & 3);
               const uint64_t idx = (bh * N + (qc < N ? qc : 0)) * (uint64_t)N + (key & ~3);
-              hlo = rng_pair(rk, idx);
-              hhi = rng_pair(rk, idx + 2);
-            }
-            u32x4 kw4 = {0u, 0u, 0u, 0u};
-            if (DM == 1) kw4 = *(const u32x4*)(Kb + kword[kt] * FB_KBP + 16 * j + 4 * fq);
-            f32x4 p;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              p[r] = (FULL || kv[kt]) ? __builtin_amdgcn_exp2f(fmaf(sv[r], c2, -l4[r])) : 0.f;
-            if (!FULL && 16 * j + 16 > N) {
+              const uint32_t hlo = rng_pair(rk, idx), hhi = rng_pair(rk, idx + 2);
+              f32x4 p;
 #pragma unroll
               for (int r = 0; r < 4; ++r)
-                if (16 * j + 4 * fq + r >= N) p[r] = 0.f;
-            }
+                p[r] = (FULL || kv[kt]) ? __builtin_amdgcn_exp2f(fmaf(sv[r], c2, -l4[r])) : 0.f;
+              if (!FULL && 16 * j + 16 > N) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              float kp = 1.f;
-              if constexpr (DM == 1) {
-                kp = ((kw4[r] >> kshift[kt]) & 1u) ? dscale : 0.f;
-              } else if constexpr (DM == 2) {
+                for (int r = 0; r < 4; ++r)
+                  if (16 * j + 4 * fq + r >= N) p[r] = 0.f;
+              }
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
                 const int src = (lane & ~3) | r;
                 const uint32_t lo = __shfl(hlo, src, 64), hi = __shfl(hhi, src, 64);
                 const uint32_t word = (key & 2) ? hi : lo;
                 const uint32_t u16 = (key & 1) ? (word >> 16) : (word & 0xffffu);
-                kp = u16 >= thr ? dscale : 0.f;
-              }
-              if constexpr (DM == 0) {
-                pd[bq][kt][r] = p[r];
-                dsv[bq][kt][r] = p[r] * (dp[r] - d4[r]);
-              } else {
+                const float kp = u16 >= thr ? dscale : 0.f;
                 pd[bq][kt][r] = p[r] * kp;
                 dsv[bq][kt][r] = p[r] * fmaf(dp[r], kp, -d4[r]);
               }
@@ -1387,15 +1216,12 @@ __global__ __launch_bounds__(FB_WAVES * 64) void mhsa_bwd_fused(
 
 static bool v2_ok(int dt, int hd, int N) { return dt == HVIT_BF16 && hd == 64 && N <= V2_KMAX && N % 4 == 0; }
 static bool v2_big(int N) { return N > 256; }  // the KMAX = 512 instantiations
-// waves per v2 workgroup: 16 = all queries (keys) of a (b, h) in one
-// workgroup, K/V (Q/dO) staged once.  Measured: two 8-wave workgroups per
-// (b, h) are slower both at B*H = 256 (default, B=32) and at B*H = 192
-// (config 5, B=16: 20.6 -> 21.5 us per layer); HVIT_ATTN_WAVES = 4 / 8 / 16
-// overrides (A/B only).  The one place the wave count is chosen: the launches
-// and the bias-partial row count both use it, so an unsupported value (clamped
-// to 4, the template the launches fall back to) cannot size the rows apart
-// from the grid.
-// (N > 256 takes the KMAX = 512 kernels, instantiated for 16 waves only)
+// Waves per v2 workgroup.  16 = 256 queries (keys): all of a (b, h) with
+// N <= 256 in one workgroup, K/V (Q/dO) staged once (two 8-wave workgroups per
+// (b, h) measured slower at B*H = 256 and at B*H = 192: 20.6 -> 21.5 us per
+// layer).  The KMAX = 512 forward runs 8 (at 16 the 128-VGPR budget spilled).
+// The launches and the bias-partial row count both read these.
+constexpr int V2_WAVES = 16, V2_FWD_BIG_WAVES = 8;
 // the single-pass backward (mhsa_bwd_fused) for N <= 256; hvit_gemm_tune(4, 0)
 // selects the dQ + dK/dV kernel pair (tests)
 int& attn_fused_ref() {
@@ -1403,27 +1229,20 @@ int& attn_fused_ref() {
   return v;
 }
 static bool v2_fused(int N) { return attn_fused_ref() != 0 && !v2_big(N); }
-static int v2_waves(int N) {
-  (void)N;
-  return 16;  // (8-wave workgroups measured slower at B·H = 256 and 192)
-}
 
 // ------------------------------------------------------------------- host ---
 template <typename T, int HD>
 static int mhsa_fwd_t(const void* qkv, void* o, float* lse, float* probs, int B, int N, int H,
                       float scale, const hvit_dropout_t* dr, hipStream_t st) {
-  uint32_t thr = dr ? drop_threshold(dr->p) : 0;
-  float ds = (dr && dr->p > 0.f) ? 1.f / (1.f - dr->p) : 1.f;
-  const DSeed seed = dseed(dr);
-  uint32_t site = dr ? dr->site : 0;
+  const DropArgs da = drop_args(dr);
   dim3 g(cdiv(N, AT_TILE), H, B);
   hipLaunchKernelGGL((mhsa_fwd_kernel<T, HD>), g, dim3(AT_THREADS), 0, st, (const T*)qkv, (T*)o, lse, B,
-                     N, H, scale, thr, ds, seed, site);
+                     N, H, scale, da.thr, da.dscale, da.seed, da.site);
   HVIT_LAUNCH_CHECK();
   if (probs) {
     hipLaunchKernelGGL((mhsa_dq_kernel<T, HD, true>), g, dim3(AT_THREADS), 0, st, (const T*)qkv,
                        (const T*)nullptr, lse, (const float*)nullptr, (T*)nullptr, probs, B, N, H,
-                       scale, thr, ds, seed, site);
+                       scale, da.thr, da.dscale, da.seed, da.site);
     HVIT_LAUNCH_CHECK();
   }
   return HVIT_OK;
@@ -1433,10 +1252,7 @@ template <typename T, int HD>
 static int mhsa_bwd_t(const void* qkv, const void* o, const void* dout, const float* lse,
                       float* delta, void* dqkv, int B, int N, int H, float scale,
                       const hvit_dropout_t* dr, hipStream_t st) {
-  uint32_t thr = dr ? drop_threshold(dr->p) : 0;
-  float ds = (dr && dr->p > 0.f) ? 1.f / (1.f - dr->p) : 1.f;
-  const DSeed seed = dseed(dr);
-  uint32_t site = dr ? dr->site : 0;
+  const DropArgs da = drop_args(dr);
   long rows = (long)B * N * H;
   hipLaunchKernelGGL((mhsa_delta_kernel<T, HD>), dim3(cdiv(rows, 4)), dim3(256), 0, st, (const T*)o,
                      (const T*)dout, delta, B, N, H);
@@ -1444,11 +1260,11 @@ static int mhsa_bwd_t(const void* qkv, const void* o, const void* dout, const fl
   dim3 g(cdiv(N, AT_TILE), H, B);
   hipLaunchKernelGGL((mhsa_dq_kernel<T, HD, false>), g, dim3(AT_THREADS), 0, st, (const T*)qkv,
                      (const T*)dout, lse, (const float*)delta, (T*)dqkv, (float*)nullptr, B, N, H,
-                     scale, thr, ds, seed, site);
+                     scale, da.thr, da.dscale, da.seed, da.site);
   HVIT_LAUNCH_CHECK();
   hipLaunchKernelGGL((mhsa_dkv_kernel<T, HD>), g, dim3(AT_THREADS), 0, st, (const T*)qkv,
-                     (const T*)dout, lse, (const float*)delta, (T*)dqkv, B, N, H, scale, thr, ds,
-                     seed, site);
+                     (const T*)dout, lse, (const float*)delta, (T*)dqkv, B, N, H, scale, da.thr,
+                     da.dscale, da.seed, da.site);
   HVIT_LAUNCH_CHECK();
   return HVIT_OK;
 }
@@ -1474,19 +1290,14 @@ static int mhsa_fwd_impl(int dt, const void* qkv, int B, int N, int H, int hd, f
   HVIT_CHECK(dt == HVIT_F32 || dt == HVIT_BF16, "hvit_mhsa_fwd: bad dtype");
   hipStream_t st = (hipStream_t)stream;
   if (v2_ok(dt, hd, N) && !probs) {
-    const hvit_dropout_t* dr = dropout;
-    const uint32_t thr = dr ? drop_threshold(dr->p) : 0;
-    const float ds = (dr && dr->p > 0.f) ? 1.f / (1.f - dr->p) : 1.f;
-    const int wv = v2_waves(N);
+    const DropArgs da = drop_args(dropout);
     auto go = [&](auto kern, int waves) {
       hipLaunchKernelGGL(kern, dim3(cdiv(N, 16 * waves), H, B), dim3(64 * waves), 0, st, (const bf16_t*)qkv,
-                         (bf16_t*)o, lse, N, H, scale, thr, ds, dseed(dr), dr ? dr->site : 0u, keep_bits);
+                         (bf16_t*)o, lse, N, H, scale, da.thr, da.dscale, da.seed, da.site, keep_bits);
     };
-    if (v2_big(N)) go(mhsa_fwd_v2<8, 512>, 8);
-    else if (wv == 16 && N == 256) go(mhsa_fwd_v2<16, 256, true>, 16);
-    else if (wv == 16) go(mhsa_fwd_v2<16, 256>, 16);
-    else if (wv == 8) go(mhsa_fwd_v2<8, 256>, 8);
-    else go(mhsa_fwd_v2<4, 256>, 4);
+    if (v2_big(N)) go(mhsa_fwd_v2<V2_FWD_BIG_WAVES, 512>, V2_FWD_BIG_WAVES);
+    else if (N == 256) go(mhsa_fwd_v2<V2_WAVES, 256, true>, V2_WAVES);
+    else go(mhsa_fwd_v2<V2_WAVES, 256>, V2_WAVES);
     HVIT_LAUNCH_CHECK();
     return HVIT_OK;
   }
@@ -1496,7 +1307,7 @@ static int mhsa_fwd_impl(int dt, const void* qkv, int B, int N, int H, int hd, f
 // partial rows of the fused bias gradient per sample: one per v2 workgroup
 // along the token axis; one per sample otherwise
 static long long mhsa_bias_rows_per_sample(int dt, int hd, int N) {
-  return v2_ok(dt, hd, N) ? (v2_fused(N) ? 1 : cdiv(N, 16 * v2_waves(N))) : 1;
+  return v2_ok(dt, hd, N) ? (v2_fused(N) ? 1 : cdiv(N, 16 * V2_WAVES)) : 1;
 }
 
 static int mhsa_bwd_impl(int dt, const void* qkv, const void* o, const void* dout, const float* lse, int B, int N,
@@ -1509,42 +1320,37 @@ static int mhsa_bwd_impl(int dt, const void* qkv, const void* o, const void* dou
   HVIT_CHECK(dt == HVIT_F32 || dt == HVIT_BF16, "hvit_mhsa_bwd: bad dtype");
   hipStream_t st = (hipStream_t)stream;
   if (v2_ok(dt, hd, N)) {
-    const hvit_dropout_t* dr = dropout;
-    const uint32_t thr = dr ? drop_threshold(dr->p) : 0;
-    const float ds = (dr && dr->p > 0.f) ? 1.f / (1.f - dr->p) : 1.f;
-    const DSeed seed = dseed(dr);
-    const uint32_t site = dr ? dr->site : 0u;
-    auto go = [&](auto dqk, auto dkvk, int waves) {
-      dim3 g(cdiv(N, 16 * waves), H, B);
-      hipLaunchKernelGGL(dqk, g, dim3(64 * waves), 0, st, (const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)dout,
-                         lse, delta_ws, (bf16_t*)dqkv, N, H, scale, thr, ds, seed, site, keep_bits, dbias);
-      hipLaunchKernelGGL(dkvk, g, dim3(64 * waves), 0, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse,
-                         (const float*)delta_ws, (bf16_t*)dqkv, N, H, scale, thr, ds, seed, site, keep_bits, dbias);
+    const DropArgs da = drop_args(dropout);
+    auto go = [&](auto dqk, auto dkvk) {
+      dim3 g(cdiv(N, 16 * V2_WAVES), H, B);
+      hipLaunchKernelGGL(dqk, g, dim3(64 * V2_WAVES), 0, st, (const bf16_t*)qkv, (const bf16_t*)o,
+                         (const bf16_t*)dout, lse, delta_ws, (bf16_t*)dqkv, N, H, scale, da.thr, da.dscale, da.seed,
+                         da.site, keep_bits, dbias);
+      hipLaunchKernelGGL(dkvk, g, dim3(64 * V2_WAVES), 0, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse,
+                         (const float*)delta_ws, (bf16_t*)dqkv, N, H, scale, da.thr, da.dscale, da.seed, da.site,
+                         keep_bits, dbias);
     };
     if (v2_fused(N)) {
       auto fb = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(1, H, B), dim3(FB_WAVES * 64), 0, st, (const bf16_t*)qkv, (const bf16_t*)o,
-                           (const bf16_t*)dout, lse, delta_ws, (bf16_t*)dqkv, N, H, scale, thr, ds, seed, site,
-                           keep_bits, dbias);
+                           (const bf16_t*)dout, lse, delta_ws, (bf16_t*)dqkv, N, H, scale, da.thr, da.dscale, da.seed,
+                           da.site, keep_bits, dbias);
       };
-      const int dm = !thr ? 0 : keep_bits ? 1 : 2;
+      const int dm = !da.thr ? V2_KEEP_NONE : keep_bits ? V2_KEEP_BITS : V2_KEEP_HASH;
       if (N == 256) {
-        if (dm == 0) fb(mhsa_bwd_fused<true, 0>);
-        else if (dm == 1) fb(mhsa_bwd_fused<true, 1>);
-        else fb(mhsa_bwd_fused<true, 2>);
+        if (dm == V2_KEEP_NONE) fb(mhsa_bwd_fused<true, V2_KEEP_NONE>);
+        else if (dm == V2_KEEP_BITS) fb(mhsa_bwd_fused<true, V2_KEEP_BITS>);
+        else fb(mhsa_bwd_fused<true, V2_KEEP_HASH>);
       } else {
-        if (dm == 0) fb(mhsa_bwd_fused<false, 0>);
-        else if (dm == 1) fb(mhsa_bwd_fused<false, 1>);
-        else fb(mhsa_bwd_fused<false, 2>);
+        if (dm == V2_KEEP_NONE) fb(mhsa_bwd_fused<false, V2_KEEP_NONE>);
+        else if (dm == V2_KEEP_BITS) fb(mhsa_bwd_fused<false, V2_KEEP_BITS>);
+        else fb(mhsa_bwd_fused<false, V2_KEEP_HASH>);
       }
       HVIT_LAUNCH_CHECK();
       return HVIT_OK;
     }
-    const int wv = v2_waves(N);
-    if (v2_big(N)) go(mhsa_dq_v2<16, 512>, mhsa_dkv_v2<16, 512>, 16);
-    else if (wv == 16) go(mhsa_dq_v2<16, 256>, mhsa_dkv_v2<16, 256>, 16);
-    else if (wv == 8) go(mhsa_dq_v2<8, 256>, mhsa_dkv_v2<8, 256>, 8);
-    else go(mhsa_dq_v2<4, 256>, mhsa_dkv_v2<4, 256>, 4);
+    if (v2_big(N)) go(mhsa_dq_v2<V2_WAVES, 512>, mhsa_dkv_v2<V2_WAVES, 512>);
+    else go(mhsa_dq_v2<V2_WAVES, 256>, mhsa_dkv_v2<V2_WAVES, 256>);
     HVIT_LAUNCH_CHECK();
     return HVIT_OK;
   }

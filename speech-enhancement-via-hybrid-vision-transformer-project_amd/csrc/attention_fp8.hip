@@ -22,6 +22,7 @@
 // recipe: fp8 forward, bf16 backward) -- sees the forward's mask; with
 // keep_bits the forward also stores the mask in the bf16 kernel's keep-bit
 // layout, so that backward reads it instead of re-hashing.
+#include "attention_tile.h"
 #include "common.h"
 
 namespace hvit {
@@ -63,12 +64,6 @@ __device__ __forceinline__ uint2 to_f8(const u32x4& u, float s) {
   r.y = f8x4(__uint_as_float(u[2] << 16) * s, __uint_as_float(u[2] & 0xffff0000u) * s,
              __uint_as_float(u[3] << 16) * s, __uint_as_float(u[3] & 0xffff0000u) * s);
   return r;
-}
-// dropout multipliers of keys kj..kj+3 of query qi (the bf16 kernel's v2_keep)
-__device__ __forceinline__ f32x4 keep4q(uint64_t bh, int N, int qi, int kj, uint32_t thr, float dscale,
-                                       unsigned long long seed, uint32_t site) {
-  const uint64_t idx = (bh * N + qi) * (uint64_t)N + kj;
-  return keep4_at(rng_key(seed, site), idx, thr, dscale);
 }
 
 template <int WAVES>
@@ -192,8 +187,7 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_fp8_kernel(const bf16_t* 
 #pragma unroll
   for (int t = 0; t < 4; ++t) ot[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int qq = q < N ? q : 0;
-  // keep bits (mhsa_fwd_v2's layout, one 256-key chunk): bit 4j + r of this
-  // lane's 64-bit word = keep(q, key 16j + 4fq + r)
+  // this lane's keep-bit pair (attention_tile.h's layout, one 256-key chunk)
   unsigned long long kw = 0ull;
 #pragma unroll
   for (int kb = 0; kb < F8_KMAX / 128; ++kb) {
@@ -206,11 +200,11 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_fp8_kernel(const bf16_t* 
         // 0/1 keep mask only: 256 P stays <= 256 < 448 (e4m3 max) for any p;
         // the 1/(1-p) scale is folded into the output's 1/sum below
         if (thr && j < nkt) {
-          const f32x4 k4 = keep4q(bh, N, qq, 16 * j + 4 * fq, thr, 1.f, seed, site);
+          const f32x4 k4 = v2_keep(bh, N, qq, 16 * j + 4 * fq, thr, 1.f, seed, site);
           p *= k4;
           kw |= (unsigned long long)((k4[0] > 0.f ? 1u : 0u) | (k4[1] > 0.f ? 2u : 0u) | (k4[2] > 0.f ? 4u : 0u) |
                                      (k4[3] > 0.f ? 8u : 0u))
-                << (4 * j);
+                << kb_nibble(j);
         }
         pb[m] = (int)f8x4(p[0], p[1], p[2], p[3]);
       }
@@ -226,17 +220,9 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_fp8_kernel(const bf16_t* 
     }
   }
   if (q < N) {
-    bf16_t* op = o + ((long)b * N + q) * D + h * 64;
-    const float oinv = thr ? inv * dscale : inv;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      uint2 u;
-      u.x = f2bf2(ot[t][0] * oinv, ot[t][1] * oinv);
-      u.y = f2bf2(ot[t][2] * oinv, ot[t][3] * oinv);
-      *(uint2*)(op + 16 * t + 4 * fq) = u;
-    }
+    v2_store_row(o + ((long)b * N + q) * D + h * 64, ot, thr ? inv * dscale : inv, fq);
     if (fq == 0) lse[bh * N + q] = (mx + log2f(sum)) * 0.6931471805599453f;
-    if (kbits && thr) *(uint2*)(kbits + ((bh * N + q) * 4 + fq) * 2) = make_uint2((uint32_t)kw, (uint32_t)(kw >> 32));
+    if (kbits && thr) *(uint2*)(kbits + kb_pair(0, 0, bh * N, q, fq)) = make_uint2((uint32_t)kw, (uint32_t)(kw >> 32));
   }
 }
 
@@ -305,8 +291,6 @@ __device__ __forceinline__ uint32_t f8w(uint32_t a, uint32_t b, float inv) {
 __device__ __forceinline__ uint2 f8_bf(const u32x4& u, float inv) {
   return make_uint2(f8w(u[0], u[1], inv), f8w(u[2], u[3], inv));
 }
-// MFMA result -> VALU read distance on a taken branch edge (attention.hip v2_settle)
-__device__ __forceinline__ void f8_settle(f32x4& a) { asm volatile("s_nop 7\n\ts_nop 3" : "+v"(a)); }
 
 // FULL: N == 256 (every key tile whole, every query in range)
 template <int WAVES, bool FULL>
@@ -416,7 +400,7 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_fp8_v2(const bf16_t* __re
                                                      0, 0);
       a = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(__builtin_bit_cast(long, (uint2){kf[2], kf[3]}), q8[1], a, 0,
                                                      0, 0);
-      f8_settle(a);
+      v2_settle(a);  // (the MFMA result read on a taken branch edge)
       if (!FULL && 16 * j + 16 > N) {  // wave-uniform: only a partial last tile
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -451,7 +435,7 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_fp8_v2(const bf16_t* __re
   const uint32_t rk = rng_key(seed, site);
   const uint64_t qrow = (bh * N + (qin ? q : 0)) * (uint64_t)N;
   const uint32_t hq = (uint32_t)(qrow >> 1) + 2u * (uint32_t)fq;
-  unsigned long long kw = 0ull;  // bit 4j + r = keep(q, key 16j + 4fq + r)
+  unsigned long long kw = 0ull;  // this lane's keep-bit pair (one chunk)
   const char* vrow = Vt + frow * F8V_VP + 32 * fq;
 #pragma unroll
   for (int kb = 0; kb < F8_KMAX / 128; ++kb) {
@@ -463,16 +447,7 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_fp8_v2(const bf16_t* __re
         f32x4 p = (j < nkt) ? st[j] : (f32x4){0.f, 0.f, 0.f, 0.f};
         if (thr && j < nkt) {
           // rng_pair(rk, qrow + 16j + 4fq) and (.. + 2): even terms, 32-bit pair index
-          const uint32_t x0 = hq + (uint32_t)(8 * j);
-          const uint32_t h0 = hash32(rk ^ x0), h1 = hash32(rk ^ (x0 + 1u));
-          const bool k0 = (h0 & 0xffffu) >= thr, k1 = (h0 >> 16) >= thr;
-          const bool k2 = (h1 & 0xffffu) >= thr, k3 = (h1 >> 16) >= thr;
-          p[0] = k0 ? p[0] : 0.f;
-          p[1] = k1 ? p[1] : 0.f;
-          p[2] = k2 ? p[2] : 0.f;
-          p[3] = k3 ? p[3] : 0.f;
-          kw |= (unsigned long long)((uint32_t)k0 | ((uint32_t)k1 << 1) | ((uint32_t)k2 << 2) | ((uint32_t)k3 << 3))
-                << (4 * j);
+          kw |= (unsigned long long)v2_keep_step(rk, hq + (uint32_t)(8 * j), thr, p) << kb_nibble(j);
         }
         pb[m] = f8x4_pos(p);
       }
@@ -488,18 +463,10 @@ __global__ __launch_bounds__(WAVES * 64) void mhsa_fwd_fp8_v2(const bf16_t* __re
     }
   }
   if (qin) {
-    bf16_t* op = o + ((long)b * N + q) * D + h * 64;
     const float inv = 1.f / sum;
-    const float oinv = thr ? inv * dscale : inv;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      uint2 u;
-      u.x = f2bf2(ot[t][0] * oinv, ot[t][1] * oinv);
-      u.y = f2bf2(ot[t][2] * oinv, ot[t][3] * oinv);
-      *(uint2*)(op + 16 * t + 4 * fq) = u;
-    }
+    v2_store_row(o + ((long)b * N + q) * D + h * 64, ot, thr ? inv * dscale : inv, fq);
     if (fq == 0) lse[bh * N + q] = (mxs - 8.f + log2f(sum)) * 0.6931471805599453f;
-    if (kbits && thr) *(uint2*)(kbits + ((bh * N + q) * 4 + fq) * 2) = make_uint2((uint32_t)kw, (uint32_t)(kw >> 32));
+    if (kbits && thr) *(uint2*)(kbits + kb_pair(0, 0, bh * N, q, fq)) = make_uint2((uint32_t)kw, (uint32_t)(kw >> 32));
   }
 }
 
@@ -533,14 +500,12 @@ extern "C" int hvit_mhsa_fwd_fp8_kb(const void* qkv, int B, int N, int H, int hd
              "hvit_mhsa_fwd_fp8: keep_bits alignment / N %% 4 (the bf16 backward's keep-bit layout)");
   // P is held as 256 * P * keep (0/1) in e4m3 (max 448), 1/(1-p) applied with
   // the normaliser: no saturation for any dropout p
-  const uint32_t thr = dropout ? drop_threshold(dropout->p) : 0;
-  const float ds = (dropout && dropout->p > 0.f) ? 1.f / (1.f - dropout->p) : 1.f;
+  const DropArgs da = drop_args(dropout);
   const int form = fp8_form_ref();
-  const uint32_t site = dropout ? dropout->site : 0u;
   if (form == 1 || form == 2) {
     auto go = [&](auto kern, int waves) {
       hipLaunchKernelGGL(kern, dim3(cdiv(N, 16 * waves), H, B), dim3(64 * waves), 0, (hipStream_t)stream,
-                         (const bf16_t*)qkv, (bf16_t*)o, lse, N, H, scale, thr, ds, dseed(dropout), site, keep_bits);
+                         (const bf16_t*)qkv, (bf16_t*)o, lse, N, H, scale, da.thr, da.dscale, da.seed, da.site, keep_bits);
     };
     if (form == 2) N == 256 ? go(mhsa_fwd_fp8_v2<8, true>, 8) : go(mhsa_fwd_fp8_v2<8, false>, 8);
     else N == 256 ? go(mhsa_fwd_fp8_v2<16, true>, 16) : go(mhsa_fwd_fp8_v2<16, false>, 16);
@@ -549,8 +514,8 @@ extern "C" int hvit_mhsa_fwd_fp8_kb(const void* qkv, int B, int N, int H, int hd
     // ones at config 5's B*H = 192: 24.4 vs 26.4 us per layer)
     constexpr int WAVES = 16;
     hipLaunchKernelGGL(mhsa_fwd_fp8_kernel<WAVES>, dim3(cdiv(N, 16 * WAVES), H, B), dim3(64 * WAVES), 0,
-                       (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)o, lse, N, H, scale, thr, ds,
-                       dseed(dropout), site, keep_bits);
+                       (hipStream_t)stream, (const bf16_t*)qkv, (bf16_t*)o, lse, N, H, scale, da.thr, da.dscale,
+                       da.seed, da.site, keep_bits);
   }
   HVIT_LAUNCH_CHECK();
   return HVIT_OK;

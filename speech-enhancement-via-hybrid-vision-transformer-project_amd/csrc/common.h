@@ -146,6 +146,16 @@ static inline uint32_t drop_threshold(float p) {
   if (t > 65536.0) t = 65536.0;
   return (uint32_t)t;
 }
+// a dropout descriptor (NULL: none) as the kernels' arguments
+struct DropArgs {
+  uint32_t thr;  // 16-bit keep threshold, 0 = no dropout
+  float dscale;  // 1 / (1 - p)
+  DSeed seed;
+  uint32_t site;
+};
+static inline DropArgs drop_args(const hvit_dropout_t* d) {
+  return {d ? drop_threshold(d->p) : 0u, (d && d->p > 0.f) ? 1.f / (1.f - d->p) : 1.f, dseed(d), d ? d->site : 0u};
+}
 
 // ----------------------------------------------------------------- GELU(erf) --
 // GELU (erf form, as torch.nn.GELU()) without the branchy libm erff: erf by

@@ -477,7 +477,8 @@ def test_mhsa_v2_deterministic(hv, N):
 
 
 @pytest.mark.parametrize("B,N,H,p,kb", [(4, 256, 8, 0.1, True), (2, 240, 8, 0.1, False), (3, 100, 2, 0.0, False),
-                                        (2, 228, 4, 0.3, True), (2, 16, 2, 0.1, True), (1, 36, 3, 0.0, False)])
+                                        (2, 228, 4, 0.3, True), (2, 16, 2, 0.1, True), (1, 36, 3, 0.0, False),
+                                        (2, 256, 2, 0.0, False), (2, 256, 2, 0.3, False)])
 def test_mhsa_bwd_single_pass_matches_pair(hv, B, N, H, p, kb):
     """The single-pass backward (mhsa_bwd_fused, N <= 256, hvit_gemm_tune(4, 1))
     against the dQ + dK/dV kernel pair (hvit_gemm_tune(4, 0)) and the torch fp32

@@ -3,7 +3,7 @@
 Round 4's wrong attention outputs came from a VALU read of an MFMA result 1-3
 wait states after the MFMA on a taken branch edge, where gfx950 needs 8 for a
 v_mfma_f32_16x16x32_bf16 (the fix is v2_settle in
-csrc/attention.hip).  tools/mfma_hazards.py walks every control-flow path from
+csrc/attention_tile.h).  tools/mfma_hazards.py walks every control-flow path from
 every MFMA of libhvit.so; these tests keep the library clean and show that the
 scanner sees the bug it is meant to guard against.
 """
@@ -105,17 +105,19 @@ def test_library_has_no_mfma_hazards():
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_attention_without_the_settle_pad_is_flagged(tmp_path):
     """attention.hip with v2_settle emptied (the round-4 code) must fail the scan;
-    HEAD (previous test) passes it."""
-    src = open(os.path.join(CSRC, "attention.hip")).read()
-    pad = re.search(r"__device__ __forceinline__ void v2_settle\(f32x4& a\) \{[^}]*\}", src)
+    HEAD (previous test) passes it.  The pad lives in attention_tile.h: the
+    patched header goes next to a copy of attention.hip (a quoted include looks
+    there first), every other header comes from csrc."""
+    hdr = open(os.path.join(CSRC, "attention_tile.h")).read()
+    pad = re.search(r"__device__ __forceinline__ void v2_settle\(f32x4& a\) \{[^}]*\}", hdr)
     assert pad and "s_nop" in pad.group(0)
-    src = src.replace(pad.group(0), "__device__ __forceinline__ void v2_settle(f32x4& a) { (void)a; }")
-    src = src.replace('#include "', '#include "' + CSRC + "/")
+    hdr = hdr.replace(pad.group(0), "__device__ __forceinline__ void v2_settle(f32x4& a) { (void)a; }")
+    (tmp_path / "attention_tile.h").write_text(hdr)
     p = tmp_path / "attention_nosettle.hip"
-    p.write_text(src)
+    p.write_text(open(os.path.join(CSRC, "attention.hip")).read())
     obj = tmp_path / "a.o"
-    r = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-c",
-                        str(p), "-o", str(obj)], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics", "-I", CSRC,
+                        "-c", str(p), "-o", str(obj)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     viol, n_mfma, _ = H.scan([str(obj)])
     assert n_mfma > 500
