@@ -536,6 +536,39 @@ int hvit_spec_normalize(float* mag, int B, int F, int T, const int* lengths, int
 int hvit_istft(const float* mag, const float* phasor, const float* gain, const int* lengths, int B, int F, int T,
                int hop, const float* window, int L, float* wave_out, void* stream);
 
+/* Speech quality metrics on device waveforms and magnitudes (evaluation/metrics.py:
+ * compute_sisdr :100-145, compute_snr :148-184, compute_segsnr :187-243,
+ * compute_lsd :246-296).  Inputs are f32; every sum and log is f64 and the
+ * results are f64 device arrays.  The calls neither allocate nor synchronise
+ * (they can be captured in a hipGraph); ws is caller scratch of at least the
+ * matching *_ws_elems doubles, 8-byte aligned.  lengths (int32 [B], nullable:
+ * every row is L samples long) gives each row's sample count, 1 <= len_b <= L;
+ * row b is x[b, :len_b] and nothing past len_b is read, whatever the buffer
+ * holds there.  No float atomics: a row's result is bit-identical from run to
+ * run and does not depend on the rest of the batch, on L or on the strides.
+ *
+ * hvit_wave_metrics: clean, est [B, L] (row strides in elements) -> out [B, 3]
+ *   = {SI-SDR, SNR, SegSNR} in dB.
+ *   SI-SDR: with the row means removed, alpha = <e, c> / (<c, c> + eps) and
+ *     10 log10(|alpha c|^2 / (|e - alpha c|^2 + eps)), from one pass of f64 moments of c and e - c.
+ *   SNR: 10 log10(mean c^2 / (mean (e - c)^2 + eps)).
+ *   SegSNR: frames of seg_frame samples start at 0, seg_hop, ... while start <
+ *     len_b - seg_frame; a frame counts when mean c^2 > eps and mean (e - c)^2 >
+ *     eps, its 10 log10 of the ratio is clipped to [-10, 35], and the result is
+ *     the mean over the counted frames, 0 when none counts.  seg_frame must be
+ *     a multiple of seg_hop, at most 16 times it (the reference's 512 / 256).
+ *   log10(0) gives -inf as in numpy (silent clean or est).
+ * hvit_lsd: mag_a, mag_b [B, F, T] as hvit_stft_fwd writes them -> out [B] =
+ *   mean over the valid frames t < min(T, 1 + len_b / hop) (all T when lengths is
+ *   NULL) of sqrt(mean over f of (log(a + eps) - log(b + eps))^2). */
+long long hvit_wave_metrics_ws_elems(int B, int L, int seg_hop);
+int hvit_wave_metrics(const float* clean, long long clean_stride, const float* est, long long est_stride,
+                      const int* lengths, int B, int L, int seg_frame, int seg_hop, double eps, double* ws,
+                      long long ws_elems, double* out, void* stream);
+long long hvit_lsd_ws_elems(int B, int T);
+int hvit_lsd(const float* mag_a, const float* mag_b, const int* lengths, int B, int F, int T, int hop, double eps,
+             double* ws, long long ws_elems, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

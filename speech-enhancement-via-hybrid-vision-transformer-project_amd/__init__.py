@@ -8,7 +8,10 @@ plus the factory it forgot to export):
     TransformerEncoderBlock, VisionTransformer, CombinedLoss, create_loss_function,
     FusedAdamW / clip_grad_norm_ / create_optimizer (training/optimizer.py, trainer.py:170-174),
     GraphedTrainStep (the train step replayed from a hipGraph per input shape, trainer.py:142-183),
-    stft_mag / istft_mag / supported / n_frames (the device STFT / iSTFT front end, frontend.py)
+    stft_mag / istft_mag / supported / n_frames (the device STFT / iSTFT front end, frontend.py),
+    compute_sisdr / compute_snr / compute_segsnr / compute_lsd / compute_pesq / compute_stoi /
+    compute_all_metrics / print_metrics (evaluation/metrics.py on the host), wave_metrics / lsd /
+    all_metrics_batch (the same scores on GPU batches, metrics.py) and Evaluator (evaluation/evaluator.py)
 """
 
 from .hybrid_vit import (  # noqa: F401
@@ -29,6 +32,20 @@ from .optim import FusedAdamW, clip_grad_norm_, create_optimizer  # noqa: F401
 from .train_step import GraphedTrainStep  # noqa: F401
 from .config import load_all_configs, load_config, merge_configs  # noqa: F401
 from .frontend import istft_mag, n_frames, stft_mag, supported  # noqa: F401
+from .metrics import (  # noqa: F401
+    all_metrics_batch,
+    compute_all_metrics,
+    compute_lsd,
+    compute_pesq,
+    compute_segsnr,
+    compute_sisdr,
+    compute_snr,
+    compute_stoi,
+    lsd,
+    print_metrics,
+    wave_metrics,
+)
+from .evaluator import Evaluator  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = [
@@ -36,4 +53,6 @@ __all__ = [
     "PositionalEncoding", "MultiHeadSelfAttention", "TransformerEncoderBlock", "VisionTransformer",
     "CombinedLoss", "create_loss_function", "FusedAdamW", "clip_grad_norm_", "create_optimizer", "GraphedTrainStep",
     "load_all_configs", "load_config", "merge_configs", "stft_mag", "istft_mag", "supported", "n_frames",
+    "compute_sisdr", "compute_snr", "compute_segsnr", "compute_lsd", "compute_pesq", "compute_stoi",
+    "compute_all_metrics", "print_metrics", "wave_metrics", "lsd", "all_metrics_batch", "Evaluator",
 ]

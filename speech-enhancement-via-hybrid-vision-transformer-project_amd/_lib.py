@@ -28,6 +28,7 @@ vp = C.c_void_p
 i32 = C.c_int
 i64 = C.c_longlong
 f32 = C.c_float
+f64 = C.c_double
 
 
 class Dropout(C.Structure):
@@ -168,6 +169,10 @@ _SIGS = {
     "hvit_stft_fwd": ([vp, i64, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp], i32),
     "hvit_spec_normalize": ([vp, i32, i32, i32, vp, i32, vp, i32, vp], i32),
     "hvit_istft": ([vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp], i32),
+    "hvit_wave_metrics_ws_elems": ([i32, i32, i32], i64),
+    "hvit_wave_metrics": ([vp, i64, vp, i64, vp, i32, i32, i32, i32, f64, vp, i64, vp, vp], i32),
+    "hvit_lsd_ws_elems": ([i32, i32], i64),
+    "hvit_lsd": ([vp, vp, vp, i32, i32, i32, i32, f64, vp, i64, vp, vp], i32),
 }
 
 EXPORTED = sorted(k for k in _SIGS)

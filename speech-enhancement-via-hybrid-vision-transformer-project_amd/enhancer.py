@@ -95,32 +95,29 @@ class AudioEnhancer:
         return out.astype(np.float32)
 
     @torch.no_grad()
-    def _enhance_device(self, clips, normalize: bool):
-        """Clips of one frame count through the device front end as one batch:
-        host peak normalisation, one upload, stft_mag (max-normalised) ->
-        model -> istft_mag with gain = mag_max * max_val taken from the
-        kernel's stats on the device (no read-back before the download)."""
+    def _enhance_device_tensor(self, clips, normalize: bool):
+        """Non-empty clips of one frame count through the device front end as
+        one batch: host peak normalisation, one upload, stft_mag
+        (max-normalised) -> model -> istft_mag with gain = mag_max * max_val
+        taken from the kernel's stats on the device (no read-back).  Returns
+        the enhanced batch ``[B, Lmax]`` (row r is clip r followed by zeros) and
+        the int32 lengths, both on the device."""
         from . import frontend as FE
 
         lens = [int(c.size) for c in clips]
-        out = [np.zeros(0, dtype=np.float32) if n == 0 else None for n in lens]
-        idx = [i for i, n in enumerate(lens) if n > 0]
-        if not idx:
-            return out
-        Lmax = max(lens[i] for i in idx)
-        wave = np.zeros((len(idx), Lmax), dtype=np.float32)
-        peak = np.ones(len(idx), dtype=np.float32)
-        for r, i in enumerate(idx):
-            c = clips[i]
+        Lmax = max(lens)
+        wave = np.zeros((len(clips), Lmax), dtype=np.float32)
+        peak = np.ones(len(clips), dtype=np.float32)
+        for r, c in enumerate(clips):
             if normalize:
                 mv = float(np.abs(c).max())
                 if mv > 1e-8:
                     c = c / mv
                     peak[r] = mv
-            wave[r, :lens[i]] = c
+            wave[r, :lens[r]] = c
         dev = torch.device(self.device)
         w = torch.from_numpy(wave).to(dev)
-        ln = torch.as_tensor([lens[i] for i in idx], dtype=torch.int32).to(dev)
+        ln = torch.as_tensor(lens, dtype=torch.int32).to(dev)
         pk = torch.from_numpy(peak).to(dev)
         mag, phasor, stats = FE.stft_mag(w, ln, self.n_fft, self.hop_length, self.win_length, return_phasor=True,
                                          normalize="max")
@@ -128,10 +125,31 @@ class AudioEnhancer:
         enh = enh.reshape(mag.shape).float().contiguous()
         mx = stats[:, 1]
         gain = torch.where(mx > 1e-8, mx, torch.ones_like(mx)) * pk
-        y = FE.istft_mag(enh, phasor, ln, gain, self.hop_length, self.win_length, length=Lmax).cpu().numpy()
+        return FE.istft_mag(enh, phasor, ln, gain, self.hop_length, self.win_length, length=Lmax), ln
+
+    def _enhance_device(self, clips, normalize: bool):
+        """``_enhance_device_tensor`` downloaded: one float32 array per clip
+        (an empty clip stays empty)."""
+        lens = [int(c.size) for c in clips]
+        out = [np.zeros(0, dtype=np.float32) if n == 0 else None for n in lens]
+        idx = [i for i, n in enumerate(lens) if n > 0]
+        if not idx:
+            return out
+        y = self._enhance_device_tensor([clips[i] for i in idx], normalize)[0].cpu().numpy()
         for r, i in enumerate(idx):
             out[i] = y[r, :lens[i]].copy()
         return out
+
+    def frame_count_batches(self, lengths, batch_size: int):
+        """Index lists for ``enhance_batch``: clips grouped by frame count
+        ``1 + len // hop``, the groups in ascending order, each cut into runs of
+        at most ``batch_size`` in input order."""
+        batch_size = max(1, int(batch_size))
+        groups = {}
+        for i, n in enumerate(lengths):
+            groups.setdefault(1 + int(n) // self.hop_length, []).append(i)
+        return [members[s:s + batch_size] for _, members in sorted(groups.items())
+                for s in range(0, len(members), batch_size)]
 
     def enhance_batch(self, clips, normalize: bool = True, batch_size: int = 32):
         """Enhance a list of clips; results in input order.  Clips are grouped
@@ -142,16 +160,10 @@ class AudioEnhancer:
         clips = [np.asarray(c, dtype=np.float32) for c in clips]
         if self.frontend == "host":
             return [self.enhance(c, normalize=normalize) for c in clips]
-        batch_size = max(1, int(batch_size))
-        groups = {}
-        for i, c in enumerate(clips):
-            groups.setdefault(1 + c.size // self.hop_length, []).append(i)
         out = [None] * len(clips)
-        for _, members in sorted(groups.items()):
-            for s in range(0, len(members), batch_size):
-                part = members[s:s + batch_size]
-                for i, y in zip(part, self._enhance_device([clips[i] for i in part], normalize)):
-                    out[i] = y
+        for part in self.frame_count_batches([c.size for c in clips], batch_size):
+            for i, y in zip(part, self._enhance_device([clips[i] for i in part], normalize)):
+                out[i] = y
         return out
 
     def enhance_file(self, input_path: Union[str, Path], output_path: Union[str, Path],
