@@ -349,26 +349,18 @@ class GradAllReducer:
             # flushes, so these buckets still reduce under the encoder backward)
             HF.wgrad_after_flush(dev, lambda b=b: self._launch(b))
             return
-        ctx = contextlib.nullcontext()
-        if dev.type == "cuda" and HF.side_pending(dev):
-            # weight gradients still in flight on the side stream (functional.on_side):
-            # copy and reduce from there, after everything issued on both streams
-            s = HF.side_stream(dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            ctx = torch.cuda.stream(s)
-        with ctx:
-            # the gradients not already in the bucket (biases, norms, sliced rows, accumulated ones):
-            # one multi-tensor copy instead of a copy launch per tensor (~85 per step at ~5 us each)
-            dsts, srcs = [], []
-            for p, o in zip(ps, offs):
-                v = self._view(p)
-                dst = flat[o:o + v.numel()].view_as(v)
-                if dst.data_ptr() != v.data_ptr():
-                    dsts.append(dst)
-                    srcs.append(v)
-            if dsts:
-                torch._foreach_copy_(dsts, srcs)
-            self.works[b] = dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self._coll_group(), async_op=True)
+        # the gradients not already in the bucket (biases, norms, sliced rows, accumulated ones):
+        # one multi-tensor copy instead of a copy launch per tensor (~85 per step at ~5 us each)
+        dsts, srcs = [], []
+        for p, o in zip(ps, offs):
+            v = self._view(p)
+            dst = flat[o:o + v.numel()].view_as(v)
+            if dst.data_ptr() != v.data_ptr():
+                dsts.append(dst)
+                srcs.append(v)
+        if dsts:
+            torch._foreach_copy_(dsts, srcs)
+        self.works[b] = dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self._coll_group(), async_op=True)
 
     def finish(self):
         """Wait for every bucket (launching any whose hooks did not fire, e.g.

@@ -345,11 +345,6 @@ def wgrad_tickets(M, N, K) -> int:
 
 
 def linear_wgrad_deferred(dt, dy, x, M, N, K, tag="vit_linear_wgrad", dest=None, side: Optional[Deferred] = None):
-    if not DEFER:  # A/B: the two-launch form (an incoming side job summed first)
-        if side is not None:
-            call("hvit_sum_slabs_strided", side.job.src, side.job.splits, side.job.stride, side.job.n, side.job.dst,
-                 stream_ptr())
-        return linear_wgrad(dt, dy, x, M, N, K, tag=tag, dest=dest), None
     """dw [N, K] = dy^T x (f32) with the split-K slab sum deferred: returns
     (dw, Deferred); dw is final once the Deferred has been passed as the side
     job of the next hvit_linear_fwd / _dgrad epilogue on this stream.
@@ -401,14 +396,11 @@ def linear_wgrad(dt, dy, x, M, N, K, bias=False, tag="linear_wgrad", tickets=Non
     return (dw, db) if bias else dw
 
 
-def linear_wgrad_bias_deferred(dt, dy, x, M, N, K, tag="linear_wgrad", out=None):
+def linear_wgrad_bias_deferred(dt, dy, x, M, N, K, tag="linear_wgrad"):
     """(dw, db, Deferred or None) of a biased Linear: the tall-skinny kernel's
     [dw | db] slab sum is left to the next linear launch on this stream (pass
     the Deferred as its epilogue side job; dw and db are final once it ran)."""
-    if not DEFER:
-        dw, db = linear_wgrad(dt, dy, x, M, N, K, bias=True, out=out)
-        return dw, db, None
-    buf = out if out is not None else torch.empty(N * K + N, dtype=torch.float32, device=dy.device)
+    buf = torch.empty(N * K + N, dtype=torch.float32, device=dy.device)
     dw, db = buf[:N * K].view(N, K), buf[N * K:]
     ws_n = L.lib().hvit_wgrad_workspace(M, N, K)
     ws = torch.empty(max(ws_n, 1), dtype=torch.float32, device=dy.device)
@@ -424,21 +416,6 @@ def linear_wgrad_bias_deferred(dt, dy, x, M, N, K, tag="linear_wgrad", out=None)
     return dw, db, (Deferred(job, ws) if job.n > 0 else None)
 
 
-def _linear_wgrad_bias_maybe_side(ctx, dt, dy, x, M, N, K):
-    """(dw, db, Deferred or None) of a biased Linear (head / skip projections):
-    on the side stream when side_ok (complete there), else on the backward's
-    stream with the slab sum deferred to the data-gradient launch after it."""
-    if not side_ok(ctx.prefs):
-        return linear_wgrad_bias_deferred(dt, dy, x, M, N, K)
-    buf = torch.empty(N * K + N, dtype=torch.float32, device=dy.device)
-    with on_side(dy.device, (dy, x, buf)):
-        # the same launches, the slab sum as one of its own (the carried job's order)
-        dw, db, j = linear_wgrad_bias_deferred(dt, dy, x, M, N, K, out=buf)
-        if j is not None:
-            call("hvit_sum_slabs_strided", j.job.src, j.job.splits, j.job.stride, j.job.n, j.job.dst, stream_ptr())
-    return dw, db, None
-
-
 def dropout_scale(g, M, N, drop, rowscale, rps, out, colsum=None):
     """out = rowscale * dropout(g) in out's dtype; colsum (f32 [N], zeroed)
     += column sums of it (per-workgroup partials in a scratch slab)."""
@@ -451,121 +428,8 @@ def dropout_scale(g, M, N, drop, rowscale, rps, out, colsum=None):
              L.dt_of(out), ptr(colsum), ptr(ws), ws_n, stream_ptr())
 
 
-def linear_wgrad_now(dt, dy, x, M, N, K, tag="vit_linear_wgrad", dest=None, side: Optional["Deferred"] = None):
-    """dw [N, K] = dy^T x (f32), complete on the current stream when its
-    launches are: the weight gradient with its split-K slab sum (and an incoming
-    side job) issued back to back (the side-stream form, where no data-gradient
-    launch follows on the same stream to carry the sum)."""
-    dw, d = linear_wgrad_deferred(dt, dy, x, M, N, K, tag=tag, dest=dest, side=side)
-    if d is not None and d.job.n > 0:
-        j = d.job
-
-        def launch():
-            call("hvit_sum_slabs_strided", j.src, j.splits, j.stride, j.n, j.dst, stream_ptr())
-
-        with timed(tag, 0.0):
-            launch()
-        _record(tag, (lambda d=d, dw=dw: launch(), 0.0))  # (d, dw: the slabs and the destination stay alive)
-    return dw
-
-
-# ---------------------------------------------------------------------------
-# Weight gradients on a side stream (round 4).  A weight gradient is off the
-# critical path of the backward (nothing reads it before the optimizer), so
-# the ViT blocks issue theirs on a per-device side stream that forks from the
-# backward's stream where its operands are ready; the data-gradient chain
-# runs on concurrently.  The side stream is joined back into the stream that
-# called backward() by an autograd final callback, before the optimizer, clip
-# or the caller can read a gradient; the data-parallel reducer launches its
-# bucket all-reduces from the side stream while work is pending there.  A
-# weight gradient that a backward ACCUMULATES into an existing .grad stays on
-# the backward's stream (autograd reads it right away).  Tensors crossing the
-# streams are registered with record_stream, so the caching allocator never
-# recycles them under a pending side launch.  Graph capture forks and joins
-# the side stream like any other (parallel branches of the captured step).
-# Off by default: measured on the MI355X (B=32 graph step, tools/gpu_session.sh
-# env:HVIT_SIDE=...), the single-stream step is faster -- 5.62 vs 5.70 ms: the
-# data-gradient GEMMs already fill the 256 CUs, so the concurrent weight
-# gradients only add their split-K slab sums (a launch each on the side stream,
-# where no following launch carries them) and contend for the CUs; fewer
-# side-stream splits (HVIT_SIDE_WG 128 / 64) were slower still (5.79 / 6.10).
-SIDE = False  # True: weight gradients on the side stream (tests/test_gpu_determinism.py runs both)
-# workgroup target of the side stream's linear weight gradients (split-K
-# choice; 0 = the library default)
-SIDE_WG = 0
-_SIDE_STREAMS = {}
-_SIDE_OPEN = set()
-_SIDE_TASKS = set()  # autograd graph tasks that have the join queued
-
-
 def _dev_index(dev) -> int:
     return dev.index if dev.index is not None else torch.cuda.current_device()
-
-
-def side_stream(dev) -> "torch.cuda.Stream":
-    i = _dev_index(dev)
-    s = _SIDE_STREAMS.get(i)
-    if s is None:
-        s = _SIDE_STREAMS[i] = torch.cuda.Stream(device=i)
-    return s
-
-
-def side_pending(dev) -> bool:
-    """Side-stream work not yet joined back (during a backward)."""
-    return _dev_index(dev) in _SIDE_OPEN
-
-
-def _join_side():
-    for i in list(_SIDE_OPEN):
-        torch.cuda.current_stream(i).wait_stream(_SIDE_STREAMS[i])
-    _SIDE_OPEN.clear()
-    _SIDE_TASKS.clear()
-
-
-class on_side:
-    """``with on_side(dev, tensors):`` launches on the device's side stream,
-    ordered after everything issued so far on the current stream; ``tensors``
-    (produced or consumed across the two streams) are recorded on the side
-    stream.  Registers the join for the end of this backward."""
-
-    __slots__ = ("dev", "tensors", "ctx", "wg")
-
-    def __init__(self, dev, tensors=()):
-        self.dev, self.tensors = dev, tensors
-
-    def __enter__(self):
-        i = _dev_index(self.dev)
-        s = side_stream(self.dev)
-        s.wait_stream(torch.cuda.current_stream(i))
-        _SIDE_OPEN.add(i)
-        task = torch._C._current_graph_task_id()
-        if task not in _SIDE_TASKS:  # once per backward (also after one that raised before its join)
-            _SIDE_TASKS.add(task)
-            torch.autograd.Variable._execution_engine.queue_callback(_join_side)
-        for t in self.tensors:
-            if t is not None:
-                t.record_stream(s)
-        self.ctx = torch.cuda.stream(s)
-        self.ctx.__enter__()
-        self.wg = L.lib().hvit_gemm_tune(2, SIDE_WG) if SIDE_WG > 0 else None
-        return s
-
-    def __exit__(self, *exc):
-        if self.wg is not None:
-            L.lib().hvit_gemm_tune(2, self.wg)
-        return self.ctx.__exit__(*exc)
-
-
-def side_ok(prefs) -> bool:
-    """The weight gradients of these parameters may go to the side stream: no
-    parameter already holds a .grad that this backward would accumulate into."""
-    if not SIDE:
-        return False
-    for r in prefs:
-        p = r()
-        if p is not None and p.grad is not None:
-            return False
-    return True
 
 
 # ---------------------------------------------------------------------------
@@ -637,7 +501,7 @@ def wgrad_requeued(dev, prefs) -> bool:
 
 def wgrad_group_ok(dt, M, N, K, pref=None) -> bool:
     """The weight gradient dW[N, K] over M tokens may join the group queue."""
-    if not WGRAD_GROUP or SIDE or dt != BF16:
+    if not WGRAD_GROUP or dt != BF16:
         return False
     if pref is not None:
         p = pref()
@@ -732,10 +596,16 @@ def wgrad_enqueue(dy, x, M, N, K, dest=None, pref=None, patch=None) -> torch.Ten
         if e is None or e[0] != task:
             e = _WG_SEEN[i] = (task, set())
         e[1].add(id(p))
+    _wgrad_flush_at_end(task)
+    return dw
+
+
+def _wgrad_flush_at_end(task):
+    """Register _wgrad_flush_all as a final callback of autograd graph task
+    ``task`` (once per task; no-op outside a backward)."""
     if task >= 0 and task not in _WG_TASKS:
         _WG_TASKS.add(task)
         torch.autograd.Variable._execution_engine.queue_callback(_wgrad_flush_all)
-    return dw
 
 
 def _wgrad_flush_all():
@@ -764,10 +634,7 @@ def wgrad_after_flush(dev, fn) -> None:
     """Run ``fn()`` right after the next flush of ``dev``'s queue."""
     i = _dev_index(dev)
     _WG_AFTER.setdefault(i, []).append(fn)
-    task = torch._C._current_graph_task_id()
-    if task >= 0 and task not in _WG_TASKS:
-        _WG_TASKS.add(task)
-        torch.autograd.Variable._execution_engine.queue_callback(_wgrad_flush_all)
+    _wgrad_flush_at_end(torch._C._current_graph_task_id())
 
 
 # Partial-row sums (Deferred side jobs) whose results were handed to autograd
@@ -779,10 +646,7 @@ _SIDE_PENDING = {}  # device index -> [Deferred]
 def side_defer(job, dev):
     i = _dev_index(dev)
     _SIDE_PENDING.setdefault(i, []).append(job)
-    task = torch._C._current_graph_task_id()
-    if task >= 0 and task not in _WG_TASKS:
-        _WG_TASKS.add(task)
-        torch.autograd.Variable._execution_engine.queue_callback(_wgrad_flush_all)
+    _wgrad_flush_at_end(torch._C._current_graph_task_id())
     return job
 
 
@@ -796,9 +660,16 @@ def side_take(job, dev) -> bool:
     return False
 
 
+def sum_slabs(d: "Deferred"):
+    """Run a Deferred's slab sum as a launch of its own on the current stream
+    (no linear launch is left to carry it as an epilogue side job)."""
+    j = d.job
+    call("hvit_sum_slabs_strided", j.src, j.splits, j.stride, j.n, j.dst, stream_ptr())
+
+
 def _side_run_pending(i):
     for j in _SIDE_PENDING.pop(i, []):
-        call("hvit_sum_slabs_strided", j.job.src, j.job.splits, j.job.stride, j.job.n, j.job.dst, stream_ptr())
+        sum_slabs(j)
 
 
 def wgrad_flush(dev=None) -> None:
@@ -910,21 +781,6 @@ def conv_wgrad(dt, g: L.ConvGeom, dz, wshape, dest=None) -> torch.Tensor:
     return dw.view(wshape)
 
 
-def _conv_wgrad_maybe_side(ctx, dt, g, dz, w, srcs):
-    """A conv weight gradient on the side stream when side_ok (its operands:
-    dz and the conv input tensors behind the geometry's raw pointers), else on
-    the backward's stream; into the parameter's data-parallel slot when one is
-    published."""
-    dest = grad_dest(*ctx.wid)
-    if not side_ok(ctx.prefs):
-        return conv_wgrad(dt, g, dz, w.shape, dest)
-    if dest is None:
-        dest = torch.empty(w.shape, dtype=torch.float32, device=dz.device)
-    with on_side(dz.device, (dz, dest) + tuple(srcs)):
-        conv_wgrad(dt, g, dz, w.shape, dest)
-    return dest.view(w.shape)
-
-
 @dataclass
 class Drop:
     """A dropout site: probability, seed and site id.  ``seed_t`` (optional): the
@@ -958,9 +814,6 @@ class CastFn(torch.autograd.Function):
 
 
 SKIPGRAD = True  # False: autograd adds the skip gradients
-# the gradient at a LayerNorm output (a linear's data gradient) in the compute
-# dtype; False: f32 (the round-5 form)
-LN_DY_LOW = True
 
 
 class SkipGrad:
@@ -1064,7 +917,6 @@ class ConvBNActFn(torch.autograd.Function):
                  gamma.data_ptr(), beta.data_ptr(), dr, pool, y.data_ptr(), dt, s)
         ctx.save_for_backward(x1, x2, w, gamma, beta)
         ctx.wid = (id(w), tuple(w.shape))
-        ctx.prefs = (weakref.ref(w),)
         ctx.z, ctx.mean, ctx.invstd = z, mean, invstd
         ctx.meta = (U, pool, training, dr, dt)
         ctx.sg = sg
@@ -1091,7 +943,7 @@ class ConvBNActFn(torch.autograd.Function):
                  dz.data_ptr(), dt, sums.data_ptr(), L.ACC_ZEROED, s)
         dbeta, dgamma = sums[:Cout], sums[Cout:2 * Cout]
         g = geom(x1, C1, x2, C2, N, Hs, Ws, U, KS, 1, KS // 2, Cout)
-        dw = _conv_wgrad_maybe_side(ctx, dt, g, dz, w, (x1, x2))
+        dw = conv_wgrad(dt, g, dz, w.shape, grad_dest(*ctx.wid))
         dx1 = dx2 = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             wd = pack_conv(w, 1, dt)
@@ -1110,24 +962,19 @@ class ConvBNActFn(torch.autograd.Function):
         return (dx1, dx2, dw, dgamma, dbeta) + (None,) * 12
 
 
-# Path switches (module attributes; the tests flip some of them to compare the
-# fused form with the separate one).  Round 6 retired their environment reads:
-# every A/B they served is concluded.
+# Path switches (module attributes, no environment reads).  Every A/B is
+# concluded and a switch whose losing side nothing reached went
+# with it; the ones left each select between two paths that stay reachable.
+# LNDROP here, SKIPGRAD (above) and WGRAD_GROUP (with the group queue): the
+# tests turn them off to get the separate-launch form as their reference.
+# C1BLOCK, EVALFOLD, KEEPBITS: the path their False side selects is also the one
+# other inputs take (a first block c1block_ok refuses, an eval forward under
+# grad mode, a shape whose attention kernel keeps no bits), so removing one
+# would delete no path.
 C1BLOCK = True  # False: the unfused conv + bn_act path
 EVALFOLD = True  # False: eval convs keep z + bn_act
 KEEPBITS = True  # False: the attention backward re-hashes dropout
 LNDROP = True  # False: separate LayerNorm backward and dropout pass
-# False: ViT weight gradients reduce their split-K slabs in a launch of their
-# own and the qkv bias gradient is a column reduction of dqkv
-DEFER = True
-# False: the qkv bias gradient by a column reduction of dqkv after the attention
-# backward (instead of the backward's partial rows)
-ATTN_DB = True
-# the fc1 forward folds its dropout multiplier into the stored gelu'(h)
-# (GELU_DUAL_DK: dh = dA * [keep * scale * gelu'(h)]), so the fc2 data-gradient
-# epilogue multiplies without re-hashing the mask.  False: the round-5 form
-# (gelu'(h) stored, the mask re-hashed in the backward)
-FC1_FOLD = True
 
 
 def c1block_ok(x1, x2, w, U, pool) -> bool:
@@ -1258,13 +1105,13 @@ class PatchEmbedFn(torch.autograd.Function):
             dpos = torch.zeros(pshape, dtype=torch.float32, device=dev)
             call("hvit_reduce_rows", gd.data_ptr(), dt, N, Nt * D, Nt * D, 1, dpos.data_ptr(), s)
         g = geom(feat, C, None, 0, N, H, W, 1, Pp, Pp, 0, D)
-        if (not SIDE and dt == BF16 and wgrad_group_ok(dt, M, D, Pp * Pp * C, ctx.prefs[0])
+        if (dt == BF16 and wgrad_group_ok(dt, M, D, Pp * Pp * C, ctx.prefs[0])
                 and L.lib().hvit_linear_wgrad_group_patch_ok(dt, M, D, Pp, H, W, C)):
             # queued with the ViT blocks' weight gradients (one grouped launch)
             dw = wgrad_enqueue(gd, feat, M, D, Pp * Pp * C, grad_dest(*ctx.wid), ctx.prefs[0],
                                patch=(Pp, tuple(w.shape)))
         else:
-            dw = _conv_wgrad_maybe_side(ctx, dt, g, gd, w, (feat,))
+            dw = conv_wgrad(dt, g, gd, w.shape, grad_dest(*ctx.wid))
         dfeat = None
         if ctx.needs_input_grad[0]:
             dfeat = _empty(feat.shape, dt, dev)
@@ -1317,23 +1164,19 @@ def _ln(x2d, gw, gb, dt):
     return y, mean, rstd
 
 
-_LN_SLAB = True
-
-
 def _ln_bwd(dy, x, mean, rstd, gw, resid, zs: ZSlot):
     """zs: a zslot(2 * D) registered in the forward (dgamma | dbeta)."""
     M, D = x.shape
     dx = torch.empty((M, D), dtype=torch.float32, device=x.device)
     acc = zs.take(x.device)
     dgw, dgb = acc[:D], acc[D:2 * D]
-    ws, ws_n = None, 0
-    if _LN_SLAB:  # per-workgroup dgamma/dbeta slab + one column reduction (no same-address atomics)
-        ws_n = L.lib().hvit_layernorm_bwd_ws_elems(M, D)
-        ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
+    # per-workgroup dgamma/dbeta slab + one column reduction (no same-address atomics)
+    ws_n = L.lib().hvit_layernorm_bwd_ws_elems(M, D)
+    ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
     # read dy, x f32 (+ resid f32), write dx f32
     with timed("layernorm_bwd", float(M * D * (dy.element_size() + 8 + (4 if resid is not None else 0)))):
         call("hvit_layernorm_bwd", dy.data_ptr(), L.dt_of(dy), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-             gw.data_ptr(), M, D, ptr(resid), dx.data_ptr(), dgw.data_ptr(), dgb.data_ptr(), ptr(ws), ws_n,
+             gw.data_ptr(), M, D, ptr(resid), dx.data_ptr(), dgw.data_ptr(), dgb.data_ptr(), ws.data_ptr(), ws_n,
              L.ACC_ZEROED, stream_ptr())
     return dx, dgw, dgb
 
@@ -1384,7 +1227,7 @@ class GradHandoff:
         (``job``) to block l's first data-gradient launch, which carries it as a
         side job (a pending side job: every flush point runs it if no launch
         has; dp.GradAllReducer holds its buckets back meanwhile).  On any other
-        path of block l -- fp32, a shape the group refuses, the side stream -- that
+        path of block l -- fp32, a shape the group refuses -- that
         launch already carries a weight gradient's slab sum, so nothing is
         deferred.  ``lnrefs``: the LayerNorm's parameters -- not deferred when
         one of them already holds a .grad (autograd would add the unwritten sums
@@ -1497,7 +1340,7 @@ class ViTBlockFn(torch.autograd.Function):
         xn2, m2, r2 = _ln(x1, n2w, n2b, dt)
         W1 = cast(f1w, dt)
         # the fc1 epilogue keeps gelu'(h) (not h) for the backward -- times the
-        # dropout multiplier (FC1_FOLD) -- so the fc2 dgrad epilogue only multiplies
+        # dropout multiplier (GELU_DUAL_DK) -- so the fc2 dgrad epilogue only multiplies
         # (no erf / exp, no mask hash per element);
         # with no backward to run (eval / no-grad inference) it stores gelu(h) only
         a = _empty((M, hid), dt, dev)
@@ -1506,7 +1349,7 @@ class ViTBlockFn(torch.autograd.Function):
             _launch("vit_linear_fwd", 2.0 * M * hid * D,
                     lambda e, st=s: call("hvit_linear_fwd", dt, xn2.data_ptr(), W1.data_ptr(), f1b.data_ptr(), M, hid, D,
                                    gh.data_ptr(), dt, e, st),
-                    epilogue(act=L.ACT_GELU_DUAL_DK if FC1_FOLD else L.ACT_GELU_DUAL_D, out2=a, drop=d_fc1.c()), (a,))
+                    epilogue(act=L.ACT_GELU_DUAL_DK, out2=a, drop=d_fc1.c()), (a,))
         else:
             gh = None
             _launch("vit_linear_fwd", 2.0 * M * hid * D,
@@ -1521,8 +1364,6 @@ class ViTBlockFn(torch.autograd.Function):
                 epilogue(drop=d_fc2.c(), resid=x1, rowscale=rs2, rps=Nt), (x1, rs2))
         ctx.save_for_backward(n1w, n2w)
         ctx.wid = tuple((id(p), tuple(p.shape)) for p in (qkvw, pw, f1w, f2w))
-        # the parameters whose gradients the side stream may produce (side_ok)
-        ctx.prefs = tuple(weakref.ref(p) for p in (qkvw, qkvb, pw, f1w, f1b, f2w))
         ctx.wrefs = tuple(weakref.ref(p) for p in (qkvw, pw, f1w, f2w))  # (the grouped weight gradients)
         ctx.lnrefs = (weakref.ref(n1w), weakref.ref(n1b))
         ctx.kbits = kbits
@@ -1533,11 +1374,11 @@ class ViTBlockFn(torch.autograd.Function):
             ho_out.grp = (dt, M, D, hid, ctx.wrefs)
         ctx.ho = (ho_in if LNDROP else None, ho_out)
         ctx.t = (x2d, xn1, m1, r1, qkv, o, lse, x1, xn2, m2, r2, gh, a, Wqkv, Wp, W1, W2, rs1, rs2)
-        ctx.meta = (B, Nt, D, H, hid, scale, dt, d_attn.c(), d_proj.c(), d_fc1.c(), d_fc2.c())
+        ctx.meta = (B, Nt, D, H, hid, scale, dt, d_attn.c(), d_proj.c(), d_fc2.c())
         # LN1, LN2 (dgamma|dbeta); fc2, proj bias grads (column sums fused into the
         # two dropout passes; fc1's comes from the GELU-backward epilogue's partial rows)
         # (LN1's / LN2's slots also hold a bias grad when a dropout pass is fused, LNDROP)
-        ctx.zs = (_zs(ctx, 3 * D), _zs(ctx, 3 * D), None, _zs(ctx, D), _zs(ctx, D), _zs(ctx, 3 * D))
+        ctx.zs = (_zs(ctx, 3 * D), _zs(ctx, 3 * D), _zs(ctx, D), _zs(ctx, D))
         if want_probs:
             ctx.mark_non_differentiable(probs)
         return x2.view(B, Nt, D), probs
@@ -1546,7 +1387,7 @@ class ViTBlockFn(torch.autograd.Function):
     def backward(ctx, dx2, _dprobs=None):
         n1w, n2w = ctx.saved_tensors
         (x2d, xn1, m1, r1, qkv, o, lse, x1, xn2, m2, r2, gh, a, Wqkv, Wp, W1, W2, rs1, rs2) = ctx.t
-        B, Nt, D, H, hid, scale, dt, dra, drp, drf1, drf2 = ctx.meta
+        B, Nt, D, H, hid, scale, dt, dra, drp, drf2 = ctx.meta
         M = B * Nt
         dev = x1.device
         s = stream_ptr()
@@ -1554,7 +1395,7 @@ class ViTBlockFn(torch.autograd.Function):
         if dx2.dtype != torch.float32:
             dx2 = dx2.float()
         # MLP branch
-        zln1, zln2, _, zf2b, zpb, zqb = ctx.zs
+        zln1, zln2, zf2b, zpb = ctx.zs
         ho_in, ho_out = ctx.ho
         jho = None  # the consumer's deferred LN partial-row sum (GradHandoff.fuse), for a launch to carry
         if ho_out is not None and ho_out.g is not None:  # fused into the next consumer's LN backward
@@ -1567,33 +1408,25 @@ class ViTBlockFn(torch.autograd.Function):
             df2b = zf2b.take(dev)
             dropout_scale(dx2, M, D, drf2, rs2, Nt, g2, df2b)
         dq_id, dp_id, d1_id, d2_id = ctx.wid
-        # weight gradients: on the side stream, concurrent with this chain of data
-        # gradients (side_ok), or else on this stream with each split-K slab sum riding
-        # on the data-gradient launch that follows it (epilogue side job)
-        side = side_ok(ctx.prefs)
-        # or queued for one grouped launch with the other blocks' (wgrad_enqueue):
-        # each then carries nothing, and the bias / LayerNorm partial-row sums the
-        # weight-gradient launches carried ride on the data-gradient launches
+        # weight gradients: queued for one grouped launch with the other blocks'
+        # (wgrad_enqueue), the bias / LayerNorm partial-row sums then riding on the
+        # data-gradient launches; or else launched here, each carrying the incoming
+        # sum and leaving its own split-K slab sum to the data-gradient launch that
+        # follows it (epilogue side job)
         wq, wp, w1, w2 = ctx.wrefs
-        group = not side and vit_block_group_ok(dt, M, D, hid, ctx.wrefs)
+        group = vit_block_group_ok(dt, M, D, hid, ctx.wrefs)
         if not group and wgrad_requeued(dev, ctx.wrefs):
             # a weight shared with a block whose gradients are queued: autograd adds this block's gradient to
             # the queued one as soon as this backward returns, so the queue is written first
             wgrad_flush(dev)
 
-        def wdest(wid, N, K):
-            d = grad_dest(*wid)
-            return d if d is not None else torch.empty((N, K), dtype=torch.float32, device=dev)
+        def wgrad(dy, x, N, K, wid, pref, job):
+            """(dw [N, K], the side job for the next data-gradient launch to carry)"""
+            if group:
+                return wgrad_enqueue(dy, x, M, N, K, grad_dest(*wid), pref), job
+            return linear_wgrad_deferred(dt, dy, x, M, N, K, dest=grad_dest(*wid), side=job)
 
-        if side:
-            df2w = wdest(d2_id, D, hid)
-            with on_side(dev, (g2, a, df2w)):
-                linear_wgrad_now(dt, g2, a, M, D, hid, dest=df2w)
-            j2 = None
-        elif group:
-            df2w, j2 = wgrad_enqueue(g2, a, M, D, hid, grad_dest(*d2_id), w2), None
-        else:
-            df2w, j2 = linear_wgrad_deferred(dt, g2, a, M, D, hid, dest=grad_dest(*d2_id))
+        df2w, j2 = wgrad(g2, a, D, hid, d2_id, w2, None)
         dh = _empty((M, hid), dt, dev)
         # fc1 bias grad: the GELU-backward epilogue's column sums, one partial row per
         # 64-row block (plain stores: deterministic), summed in row order as the fc1
@@ -1602,27 +1435,18 @@ class ViTBlockFn(torch.autograd.Function):
         cparts = torch.empty((nrow, hid), dtype=torch.float32, device=dev)
         df1b = torch.empty(hid, dtype=torch.float32, device=dev)
         if jho is not None and j2 is not None:  # (one side job per launch)
-            call("hvit_sum_slabs_strided", jho.job.src, jho.job.splits, jho.job.stride, jho.job.n, jho.job.dst, s)
+            sum_slabs(jho)
             jho = None
-        e_fc2 = epilogue(act=L.ACT_MUL_AUX, aux=gh, drop=None if FC1_FOLD else drf1, colsum=cparts,
-                         side=j2 if j2 is not None else jho)
+        e_fc2 = epilogue(act=L.ACT_MUL_AUX, aux=gh, colsum=cparts, side=j2 if j2 is not None else jho)
         _launch("vit_linear_dgrad", 2.0 * M * D * hid,
                 lambda e, st=s: call("hvit_linear_dgrad", dt, g2.data_ptr(), W2.data_ptr(), M, D, hid, dh.data_ptr(), dt, e,
                                st), e_fc2, (gh, cparts))
         jc = Deferred(L.SlabSum(cparts.data_ptr(), df1b.data_ptr(), hid, hid, nrow), cparts)
-        if side:
-            df1w = wdest(d1_id, hid, D)
-            with on_side(dev, (dh, xn2, cparts, df1b, df1w)):
-                linear_wgrad_now(dt, dh, xn2, M, hid, D, dest=df1w, side=jc)
-            j1 = None
-        elif group:
-            df1w, j1 = wgrad_enqueue(dh, xn2, M, hid, D, grad_dest(*d1_id), w1), jc
-        else:
-            df1w, j1 = linear_wgrad_deferred(dt, dh, xn2, M, hid, D, dest=grad_dest(*d1_id), side=jc)
+        df1w, j1 = wgrad(dh, xn2, hid, D, d1_id, w1, jc)
         # the gradient at the LayerNorm output in the compute dtype (bf16 under the
         # bf16 model, as torch autocast's linear backward gives it): 8 MB less to
         # store and to re-read per LayerNorm backward at B=32 (dx stays f32)
-        dxn2 = _empty((M, D), dt if LN_DY_LOW else F32, dev)
+        dxn2 = _empty((M, D), dt, dev)
         e_fc1 = epilogue(side=j1)
         _launch("vit_linear_dgrad", 2.0 * M * hid * D,
                 lambda e, st=s: call("hvit_linear_dgrad", dt, dh.data_ptr(), W1.data_ptr(), M, hid, D, dxn2.data_ptr(),
@@ -1639,15 +1463,7 @@ class ViTBlockFn(torch.autograd.Function):
             dpb = zpb.take(dev)
             dropout_scale(dx1, M, D, drp, rs1, Nt, g1, dpb)
         # attention branch
-        if side:
-            dpw = wdest(dp_id, D, D)
-            with on_side(dev, (g1, o, dpw) + (jln.ws if jln is not None else ())):
-                linear_wgrad_now(dt, g1, o, M, D, D, dest=dpw, side=jln)
-            jp = None
-        elif group:
-            dpw, jp = wgrad_enqueue(g1, o, M, D, D, grad_dest(*dp_id), wp), jln
-        else:
-            dpw, jp = linear_wgrad_deferred(dt, g1, o, M, D, D, dest=grad_dest(*dp_id), side=jln)
+        dpw, jp = wgrad(g1, o, D, D, dp_id, wp, jln)
         do = _empty((M, D), dt, dev)
         e_pr = epilogue(side=jp)
         _launch("vit_linear_dgrad", 2.0 * M * D * D,
@@ -1659,31 +1475,15 @@ class ViTBlockFn(torch.autograd.Function):
         # backward (one row per workgroup on the register-resident kernels, one per
         # sample by a segmented column sum elsewhere; plain stores, summed in row
         # order: deterministic), summed as the qkv weight-gradient launch's side job
-        jb = None
-        if ATTN_DB:
-            nbr = L.lib().hvit_mhsa_bias_rows(dt, B, Nt, H, D // H)
-            bparts = torch.empty((nbr, 3 * D), dtype=torch.float32, device=dev)
-            dqkvb = torch.empty(3 * D, dtype=torch.float32, device=dev)
-            with timed("attn_bwd", 8.0 * B * H * Nt * Nt * (D // H)):
-                call("hvit_mhsa_bwd_db", dt, qkv.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), B, Nt, H,
-                     D // H, scale, dra, ptr(ctx.kbits), dqkv.data_ptr(), delta.data_ptr(), bparts.data_ptr(), s)
-            jb = Deferred(L.SlabSum(bparts.data_ptr(), dqkvb.data_ptr(), 3 * D, 3 * D, nbr), bparts)
-        else:
-            with timed("attn_bwd", 8.0 * B * H * Nt * Nt * (D // H)):
-                call("hvit_mhsa_bwd_db", dt, qkv.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), B, Nt, H,
-                     D // H, scale, dra, ptr(ctx.kbits), dqkv.data_ptr(), delta.data_ptr(), None, s)
-            dqkvb = zqb.take(dev)
-            call("hvit_reduce_rows", dqkv.data_ptr(), dt, M, 3 * D, 3 * D, 1, dqkvb.data_ptr(), s)
-        if side:
-            dqkvw = wdest(dq_id, 3 * D, D)
-            with on_side(dev, (dqkv, xn1, dqkvw, dqkvb) + ((jb.ws,) if jb is not None else ())):
-                linear_wgrad_now(dt, dqkv, xn1, M, 3 * D, D, dest=dqkvw, side=jb)
-            jq = None
-        elif group:
-            dqkvw, jq = wgrad_enqueue(dqkv, xn1, M, 3 * D, D, grad_dest(*dq_id), wq), jb
-        else:
-            dqkvw, jq = linear_wgrad_deferred(dt, dqkv, xn1, M, 3 * D, D, dest=grad_dest(*dq_id), side=jb)
-        dxn1 = _empty((M, D), dt if LN_DY_LOW else F32, dev)
+        nbr = L.lib().hvit_mhsa_bias_rows(dt, B, Nt, H, D // H)
+        bparts = torch.empty((nbr, 3 * D), dtype=torch.float32, device=dev)
+        dqkvb = torch.empty(3 * D, dtype=torch.float32, device=dev)
+        with timed("attn_bwd", 8.0 * B * H * Nt * Nt * (D // H)):
+            call("hvit_mhsa_bwd_db", dt, qkv.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), B, Nt, H,
+                 D // H, scale, dra, ptr(ctx.kbits), dqkv.data_ptr(), delta.data_ptr(), bparts.data_ptr(), s)
+        jb = Deferred(L.SlabSum(bparts.data_ptr(), dqkvb.data_ptr(), 3 * D, 3 * D, nbr), bparts)
+        dqkvw, jq = wgrad(dqkv, xn1, 3 * D, D, dq_id, wq, jb)
+        dxn1 = _empty((M, D), dt, dev)
         e_qkv = epilogue(side=jq)
         _launch("vit_linear_dgrad", 2.0 * M * 3 * D * D,
                 lambda e, st=s: call("hvit_linear_dgrad", dt, dqkv.data_ptr(), Wqkv.data_ptr(), M, 3 * D, D, dxn1.data_ptr(),
@@ -1714,7 +1514,6 @@ class HeadFn(torch.autograd.Function):
              stream_ptr())
         ctx.save_for_backward(nw)
         ctx.t = (x2d, xn, m, r, W)
-        ctx.prefs = (weakref.ref(w), weakref.ref(b))
         ctx.lnrefs = (weakref.ref(nw), weakref.ref(nb))
         ctx.meta = (B, Nt, D, C, dt)
         ctx.ho = ho if LNDROP else None
@@ -1728,8 +1527,8 @@ class HeadFn(torch.autograd.Function):
         B, Nt, D, C, dt = ctx.meta
         M = B * Nt
         dy = cast(dy, dt)
-        dw, db, jw = _linear_wgrad_bias_maybe_side(ctx, dt, dy, xn, M, C, D)
-        dxn = _empty((M, D), dt if LN_DY_LOW else F32, dy.device)
+        dw, db, jw = linear_wgrad_bias_deferred(dt, dy, xn, M, C, D)
+        dxn = _empty((M, D), dt, dy.device)
         call("hvit_linear_dgrad", dt, dy.data_ptr(), W.data_ptr(), M, C, D, dxn.data_ptr(), L.dt_of(dxn),
              epilogue(side=jw) if jw is not None else None, stream_ptr())  # (carries the wgrad's slab sum)
         if ctx.ho is not None and ctx.ho.drop is not None:  # the last block's fc2 dropout, fused
@@ -1761,7 +1560,6 @@ class SkipFn(torch.autograd.Function):
         M = N * Ho * Wo
         call("hvit_linear_fwd", dt, r.data_ptr(), W.data_ptr(), b.data_ptr(), M, Cd, Ce, y.data_ptr(), dt, None, s)
         ctx.t = (r, W)
-        ctx.prefs = (weakref.ref(w), weakref.ref(b))
         ctx.meta = (N, He, We, Ce, Ho, Wo, Cd, dt, tuple(w.shape))
         ctx.sg = sg
         return y
@@ -1774,11 +1572,11 @@ class SkipFn(torch.autograd.Function):
         dev = r.device
         s = stream_ptr()
         dy = cast(dy, dt)
-        dw, db, jw = _linear_wgrad_bias_maybe_side(ctx, dt, dy, r, M, Cd, Ce)
+        dw, db, jw = linear_wgrad_bias_deferred(dt, dy, r, M, Cd, Ce)
         dw = dw.view(wshape)
         de = None
         if jw is not None and not ctx.needs_input_grad[0]:  # no launch follows to carry the slab sum
-            call("hvit_sum_slabs_strided", jw.job.src, jw.job.splits, jw.job.stride, jw.job.n, jw.job.dst, s)
+            sum_slabs(jw)
         if ctx.needs_input_grad[0]:
             dr = _empty((N, Ho, Wo, Ce), dt, dev)
             call("hvit_linear_dgrad", dt, dy.data_ptr(), W.data_ptr(), M, Cd, Ce, dr.data_ptr(), dt,

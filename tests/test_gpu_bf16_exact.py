@@ -250,7 +250,7 @@ def test_linear_wgrad_bias_deferred_side_job(env, M, N, K):
     out = torch.empty_like(out_ref)
     L.call("hvit_linear_dgrad", L.BF16, g.data_ptr(), w.data_ptr(), M, N, K, out.data_ptr(), L.F32,
            HF.epilogue(side=job), s())
-    # the job run as a launch of its own (side-stream form): the carried order, bit for bit
+    # the job run as a launch of its own (functional.sum_slabs' form): the carried order, bit for bit
     dw2, db2, job2 = HF.linear_wgrad_bias_deferred(L.BF16, dy, x, M, N, K)
     j = job2.job
     L.call("hvit_sum_slabs_strided", j.src, j.splits, j.stride, j.n, j.dst, s())

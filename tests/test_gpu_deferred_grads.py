@@ -15,8 +15,8 @@ A2  the first grouped launch of a device inside a hipGraph capture (the ticket
     wgrad_group_init() an eager backward before the first replay must be right);
 A3  a user's post-accumulate-grad hook on a queued weight, and a Parameter
     shared by two blocks (autograd adds the two gradients at once);
-A4  two streams of one device (separate ticket counters), and SIDE = True
-    with the grouped launch left on (the group must not run).
+A4  two streams of one device (separate ticket counters), and a second
+    backward that accumulates into existing gradients (nothing is queued).
 
 Every backward under test runs right after poison_allocator(): the caching
 allocator then hands NaN-filled blocks to the next torch.empty, so a reader
@@ -465,26 +465,34 @@ def test_two_streams_have_their_own_tickets(hv):
     assert_grads_equal(_grads(mb), ref_b, "stream B")
 
 
-def test_side_stream_keeps_the_group_off(hv):
-    """SIDE = True with WGRAD_GROUP at its default: the grouped launch must not
-    run, and the gradients are those of SIDE = True, WGRAD_GROUP = False."""
+def test_second_backward_accumulates_off_the_queue(hv):
+    """A second backward into existing .grad tensors: no parameter may be queued
+    (autograd adds its gradient at once), so the whole backward takes the
+    per-Linear path and the sums are those of two per-Linear backwards.
+
+    The bar is assert_grads_close's own, scaled by max|2 * ref|: the first
+    (grouped) backward is within that helper's bar of ref, the second runs the
+    reference's own launches, so their sum is within the same bar of 2 * ref."""
     HF = _hf()
+    i = torch.cuda.current_device()
     torch.manual_seed(4)
-    m0 = hv.HybridViT(**BF16, **NODROP).to(DEV).train()
+    m = hv.HybridViT(**BF16, **NODROP).to(DEV).train()
     x, t = _batch(8, 26)
-    assert HF.WGRAD_GROUP is True and HF.SIDE is False
-    n0 = HF.WG_LAUNCHES
-    _backward(hv, copy.deepcopy(m0), x, t)
-    assert HF.WG_LAUNCHES > n0, "this model and batch take the grouped launch on the default path"
+    old = HF.WGRAD_GROUP
     try:
-        HF.SIDE = True
-        n0 = HF.WG_LAUNCHES
-        got = _backward(hv, copy.deepcopy(m0), x, t)
-        assert HF.WG_LAUNCHES == n0, "the grouped launch ran with the side stream on"
-        assert not HF._WG_QUEUE and not any(HF._SIDE_PENDING.values())
         HF.WGRAD_GROUP = False
-        ref = _backward(hv, copy.deepcopy(m0), x, t)
-        assert HF.WG_LAUNCHES == n0
+        ref = _backward(hv, m, x, t, poison=False)
     finally:
-        HF.SIDE, HF.WGRAD_GROUP = False, True
-    assert_grads_equal(got, ref, "SIDE with the group left on")
+        HF.WGRAD_GROUP = old
+    n0 = HF.WG_LAUNCHES
+    _backward(hv, m, x, t)
+    n1 = HF.WG_LAUNCHES
+    assert n1 > n0, "this model and batch take the grouped launch on the default path"
+    loss = hv.CombinedLoss()(m(x), t)
+    poison_allocator()
+    loss.backward()  # accumulates: every parameter holds a .grad
+    torch.cuda.synchronize()
+    assert HF.WG_LAUNCHES == n1, "a parameter that holds a .grad was queued"
+    assert not HF._WG_QUEUE.get(i) and not HF._SIDE_PENDING.get(i) and not HF._WG_AFTER.get(i)
+    assert HF.WG_FIXUPS == 0
+    assert_grads_close(_grads(m), {n: 2 * v for n, v in ref.items()}, "two backwards into one .grad")

@@ -1,6 +1,6 @@
 """bench.py with library tuning knobs set first (same-process A/B of a
 hvit_gemm_tune form or a functional.py path switch):
-    python tools/bench_tune.py 6=1 HF.LN_DY_LOW=0 -- --no-cpu-baseline
+    python tools/bench_tune.py 6=1 HF.WGRAD_GROUP=0 -- --no-cpu-baseline
 (``what=value`` / ``HF.NAME=int`` before ``--``, bench.py's arguments after)."""
 
 import os

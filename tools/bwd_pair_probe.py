@@ -86,7 +86,9 @@ def main():
                    L.stream_ptr())
 
         def wgrad_now():
-            return HF.linear_wgrad_now(L.BF16, dy, x, M, N, K)
+            _, j = HF.linear_wgrad_deferred(L.BF16, dy, x, M, N, K)
+            if j.job.n > 0:
+                HF.sum_slabs(j)  # (the slab sum as a launch of its own: nothing follows on this stream to carry it)
 
         def seq():
             _, j = HF.linear_wgrad_deferred(L.BF16, dy, x, M, N, K)
