@@ -147,32 +147,44 @@ long long hvit_wgrad_workspace(int M, int N, int K);                            
 long long hvit_wgrad_tickets(int M, int N, int K);
 int hvit_linear_wgrad_tk(int dt, const void* dy, const void* x, int M, int N, int K, float* dw, float* db, float* ws,
                          long long ws_elems, unsigned* tickets, long long tickets_elems, int flags, void* stream);
-/* Tuning knobs (A/B measurements, tests): what 0 = GEMM pipeline of the bf16
- * linears (-1 automatic, 0: two-stage kernels; 1-5: LDS-ring configurations,
- * gemm_ring.h); what 1 = the fused first block's matrix-core kernels (1 on, 0:
- * the VALU kernels); what 2 = workgroup target of the linear weight gradients'
- * split-K choice for the calls that follow (0: default 256; also sizes
- * hvit_wgrad_workspace); what 4 = the attention backward for bf16 / head_dim 64 /
- * N <= 256 (1: the single-pass kernel, 0: the dQ and dK/dV kernel pair); what 5
- * = the fp8 attention forward form (1: v2, 0: round 4's kernel, 2: v2 as two
- * 8-wave workgroups per (b, h)); what 9 = the A operand of the bf16 3x3 conv
- * forward / data-gradient GEMMs (0: per-tap implicit im2col, 1: the input halo
- * resident in LDS where it applies and measured faster, 2: wherever it
- * applies; results are bit-identical); what 10 = read-only, the number of
- * halo-resident launches so far.
- * Returns the previous value (-1 for an unknown knob). */
+/* Tuning knobs (A/B measurements, tests): hvit_gemm_tune(what, value) sets knob
+ * `what` and returns its previous value; a value that the ring, grouped
+ * weight-gradient or halo knob does not list changes nothing.  The numbers are
+ * the ABI; 2, 3, 6 and 8 belonged to forms
+ * that were measured and removed, return -1 like any unknown knob, and are not
+ * reused.
+ *  HVIT_TUNE_RING: GEMM pipeline of the bf16 linears (-1 automatic per shape,
+ *    0: gemm.h's two-stage kernels only, 2 / 4 / 5: one LDS-ring configuration,
+ *    csrc/gemm_ring.h).
+ *  HVIT_TUNE_C1_MFMA: the fused first block's matrix-core kernels (1 on, 0: the
+ *    VALU kernels).
+ *  HVIT_TUNE_ATTN_BWD: the attention backward for bf16 / head_dim 64 / N <= 256
+ *    (1: the single-pass kernel, 0: the dQ and dK/dV kernel pair).
+ *  HVIT_TUNE_FP8_FWD: the fp8 attention forward form (1: v2, 0: round 4's
+ *    kernel, 2: v2 as two 8-wave workgroups per (b, h)).
+ *  HVIT_TUNE_WGRAD_GROUP: the grouped weight gradients' tile configuration (0,
+ *    2 or 6, csrc/wgrad_group.hip).
+ *  HVIT_TUNE_CONV_HALO: the A operand of the bf16 3x3 conv forward / data-
+ *    gradient GEMMs (0: per-tap implicit im2col, 1: the input halo resident in
+ *    LDS where it applies and measured faster, 2: wherever it applies; results
+ *    are bit-identical).
+ *  HVIT_TUNE_CONV_HALO_COUNT: read-only, the number of halo-resident launches
+ *    so far. */
+enum {
+  HVIT_TUNE_RING = 0,
+  HVIT_TUNE_C1_MFMA = 1,
+  HVIT_TUNE_ATTN_BWD = 4,
+  HVIT_TUNE_FP8_FWD = 5,
+  HVIT_TUNE_WGRAD_GROUP = 7,
+  HVIT_TUNE_CONV_HALO = 9,
+  HVIT_TUNE_CONV_HALO_COUNT = 10
+};
 int hvit_gemm_tune(int what, int value);
 /* Diagnostics (tests): the LDS byte offset of the 16-byte channel chunk `chunk`
  * of halo pixel (hy, hx) in the halo-resident conv A image of a `rows`-row tile
  * on an H x W map of C channels (csrc/gemm_conv_halo.h), or -1 where that form
  * does not apply to the geometry.  No GPU work. */
 int hvit_conv_halo_off(int H, int W, int C, int rows, int hy, int hx, int chunk);
-/* Diagnostics only (tools/wgrad_layout_probe.py): C[M,N] = sum_k A[m,k] B[n,k]
- * as f32 split-K slabs ws[splits][M*N + M]; kca / kcb: 1 = operand stored with
- * K contiguous ([M][K] / [N][K]), 0 = [K][M] / [K][N]; cfg 0 = gemm.h's kernels,
- * 1-5 = a ring configuration (error if it does not apply). */
-int hvit_probe_gemm_splitk(int kca, int kcb, const void* a, const void* b, int M, int N, int K, int splits,
-                           float* ws, int cfg, void* stream);
 /* dw[N,K] = dy^T x; db[N] = colsum(dy) (nullable; fused when db == dw + N*K) */
 int hvit_linear_wgrad(int dt, const void* dy, const void* x, int M, int N, int K, float* dw, float* db,
                       float* ws, long long ws_elems, void* stream);

@@ -19,6 +19,9 @@ ACT_NONE, ACT_GELU_DUAL, ACT_TANH, ACT_GELU_BWD, ACT_GELU_DUAL_D, ACT_MUL_AUX, A
 ACT_GELU_DUAL_DK = 9
 ACC_ZEROED = 1
 ACC_DEFER = 2
+# hvit_gemm_tune knobs (include/hvit.h: HVIT_TUNE_*)
+TUNE_RING, TUNE_C1_MFMA, TUNE_ATTN_BWD, TUNE_FP8_FWD, TUNE_WGRAD_GROUP, TUNE_CONV_HALO, TUNE_CONV_HALO_COUNT = (
+    0, 1, 4, 5, 7, 9, 10)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HVIT_LIB selects an alternative in-tree build (kernel A/B benchmarking only)
@@ -164,7 +167,6 @@ _SIGS = {
     "hvit_rng_advance": ([vp, vp, vp], i32),
     "hvit_gemm_tune": ([i32, i32], i32),
     "hvit_conv_halo_off": ([i32, i32, i32, i32, i32, i32, i32], i32),
-    "hvit_probe_gemm_splitk": ([i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, vp], i32),
     "hvit_step_bump": ([vp, i32, f32, vp], i32),
     "hvit_stft_fwd": ([vp, i64, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp], i32),
     "hvit_spec_normalize": ([vp, i32, i32, i32, vp, i32, vp, i32, vp], i32),

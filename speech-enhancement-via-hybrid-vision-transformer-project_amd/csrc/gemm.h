@@ -898,16 +898,6 @@ extern __device__ unsigned long long g_gemm_stamps[65536 * 4];
   } while (0)
 #endif
 
-template <typename X>
-struct IsConvWF : std::false_type {};
-template <typename T>
-struct IsConvWF<LdConvWF<T>> : std::true_type {};
-#ifndef HVIT_WF_STAGES
-#define HVIT_WF_STAGES 2
-#endif
-#ifndef HVIT_BIG_OCC
-#define HVIT_BIG_OCC 2
-#endif
 // XCD-aware tile order.  Workgroups are dealt round-robin over the 8 XCDs
 // (block b and b + 8 share one XCD's 4 MiB L2), so in hardware order every
 // XCD sees tiles from all over the output and re-fetches the same A rows / B
@@ -938,11 +928,10 @@ __device__ __forceinline__ TileId tile_of(int remap) {
 // workgroups per CU), 1 = LDS-DMA with one stage buffer (three per CU), 3 =
 // three stage buffers (long K, 128x64 / 64x64 tiles)
 template <typename T, int BM, int BN, class LA, class LB, int EK, bool RS = false, int DMAK = 0>
-__global__ __launch_bounds__(GEMM_THREADS, (DMAK == 1 ? 3 : BM >= 128 ? HVIT_BIG_OCC : 2)) void gemm_kernel(LA la, LB lb, int M, int N,
+__global__ __launch_bounds__(GEMM_THREADS, (DMAK == 1 ? 3 : 2)) void gemm_kernel(LA la, LB lb, int M, int N,
                                                                                             int K, int kps, Epi ep) {
-  // the implicit-im2col weight gradient streams both operands from HBM once:
-  // deeper register prefetch (its 128x64 tiles have the registers for it)
-  using C = GemmCore<T, BM, BN, LA, LB, IsConvWF<LB>::value ? HVIT_WF_STAGES : 2>;
+  // two register-prefetch stages for every loader pair
+  using C = GemmCore<T, BM, BN, LA, LB, 2>;
   constexpr int WM = C::WM, WN = C::WN, WTM = C::WTM, WTN = C::WTN, FM = C::FM, FN = C::FN;
   // LDS-DMA K loop (DMAK kernels): dense bf16 operands, no row sums
   constexpr bool DMA =
@@ -1348,29 +1337,18 @@ inline int plan_splits(int K, int splits, int* kps_out = nullptr) {
   return K > 0 ? (K + kps - 1) / kps : 1;
 }
 
-// LDS-DMA stage buffers of the 128x64 / 64x64 kernels on long K loops
-// (hvit_gemm_tune(8, v): 3 = three buffers from DEEP_MIN_STAGES stages on, 4 = from 8 stages, 2 = two)
-inline int& dma_depth_ref() {
-  // same-box A/B (gpurun_out/r6n_dma*): two buffers 4.656-4.660 ms/step, three from 16 stages
-  // 4.543-4.551, three from 8 stages 4.509-4.524 (vit_linear_dgrad 0.784 -> 0.728, vit_linear_fwd
-  // 0.774 -> 0.741, conv_fwd 0.410 -> 0.388 ms/step)
-  static int v = 4;
-  return v;
-}
-inline int dma_depth() { return dma_depth_ref(); }
-constexpr int DEEP_MIN_STAGES = 16;
-
 // tile: 128x128 when the grid still fills the chip; 128x64 for narrow
 // outputs (N <= 64: conv layers with 64 channels); else 64x64
 inline int auto_tile(int M, int N, int splits) {
   // 128x64 also when 128x128 would leave fewer than ~1.5 workgroups per CU
   // or a half-empty last column tile (measured: 2.5 % per train step)
-  constexpr int policy = 2;  // (policies 0 / 1 measured slower: DESIGN.md §8)
+  // (without the third rule below 5.99, without the second and third 6.26 vs
+  // 5.91 ms/step: DESIGN.md §8, profiles/r2_ab/tile_policy_ab.txt)
   const long b128 = (long)cdiv(M, 128) * cdiv(N, 128) * splits;
   const long b12864 = (long)cdiv(M, 128) * cdiv(N, 64) * splits;
   if (N <= 64 && (long)cdiv(M, 128) * splits >= 160) return 12864;
-  if (policy >= 1 && N > 64 && b128 < 384 && b12864 >= 384) return 12864;
-  if (policy >= 2 && N > 64 && N % 128 != 0 && N % 64 == 0 && b12864 >= 160) return 12864;
+  if (N > 64 && b128 < 384 && b12864 >= 384) return 12864;
+  if (N > 64 && N % 128 != 0 && N % 64 == 0 && b12864 >= 160) return 12864;
   if (N > 64 && b128 >= 160) return 128;
   return 64;
 }
@@ -1423,20 +1401,19 @@ int launch_gemm(LA la, LB lb, int M, int N, int K, int splits, const Epi& ep_in,
   // the tile, every K slice a multiple of 64, vector-aligned operands)
   // (or the implicit-im2col conv A loader, LdConvF: every 64-channel stage in
   // one tap and one source, byte offsets < 2^31 -- conv_fast_ok)
+  // Not with both operands k-major (the weight gradients): the register path
+  // measured faster there (0.82 vs 1.04 ms/step)
   constexpr bool CONV_A = IsConvFBf16<LA>::value;
-  constexpr bool DMA_OK = sizeof(T) == 2 && (IsDenseBf16<LA>::value || CONV_A) && IsDenseBf16<LB>::value;
+  constexpr bool DMA_OK = sizeof(T) == 2 && (IsDenseBf16<LA>::value || CONV_A) && IsDenseBf16<LB>::value &&
+                          (LA::KC || LB::KC);
   bool all_in = false;
   if constexpr (DMA_OK) {
     const int bm = tile == 128 || tile == 12864 ? 128 : 64, bn = tile == 128 ? 128 : 64;
-    // both operands k-major (the weight gradients): the register path measured
-    // faster (1.04 vs 0.82 ms/step)
-    constexpr bool mnmn = false;
-    constexpr bool conv_dma = true;
-    bool a_ok;
-    if constexpr (CONV_A) a_ok = conv_dma;
-    else a_ok = la.vok;
+    bool a_ok = true;  // (the conv A loader's conditions are conv_fast_ok's; the register path
+                       // for it measured slower, profiles/r2_ab/conv_dma_ab.txt)
+    if constexpr (!CONV_A) a_ok = la.vok;
     all_in = ep.dma && M % bm == 0 && N % bn == 0 && kps % 64 == 0 && K % kps == 0 && a_ok && lb.vok &&
-             !ep.rs_ptr && (LA::KC || LB::KC || mnmn);
+             !ep.rs_ptr;
   }
   auto go = [&](auto ekc) {
     constexpr int EKc = decltype(ekc)::value;
@@ -1451,12 +1428,10 @@ int launch_gemm(LA la, LB lb, int M, int N, int K, int splits, const Epi& ep_in,
             // epilogue overlaps another's K loop) for the 128x128 forward kinds:
             // vit_linear_fwd 0.732 -> 0.721 ms/step.  Not for GELU_BWD (its h
             // prefetch spills at 168 VGPRs: dgrad 0.737 -> 0.780)
-            constexpr bool nb1 = true;
             // conv forward (BN statistics epilogue) too: conv_fwd 0.471 -> 0.447 ms/step;
             // not the conv data gradient (0.346 -> 0.362)
-            constexpr bool nb1c = true;
             if constexpr (BMc == 128 && BNc == 128 && (EKc == EK_GELU_DUAL || EKc == EK_STORE)) {
-              if (CONV_A ? (nb1c && ep.stats) : nb1) {
+              if (!CONV_A || ep.stats) {
                 hipLaunchKernelGGL((gemm_kernel<T, BMc, BNc, LA, LB, EKc, false, 1>), g, dim3(GEMM_THREADS), 0, st,
                                    la, lb, M, N, K, kps, ep);
                 return;
@@ -1467,8 +1442,10 @@ int launch_gemm(LA la, LB lb, int M, int N, int K, int splits, const Epi& ep_in,
               // conv_dgrad 0.376 -> 0.394 ms/step with three buffers, 72 KiB of LDS leaving
               // two workgroups per CU where the 48 KiB two-buffer kernel keeps three; the
               // patch-embedding forward, with its positional-row epilogue, does take them)
-              if (dma_depth() >= 3 && kps / 64 >= (dma_depth() == 4 ? 8 : DEEP_MIN_STAGES) &&
-                  (!CONV_A || ep.stats || ep.rowadd)) {
+              // three stage buffers from 8 stages on: two buffers 4.656-4.660 ms/step, three
+              // from 16 stages 4.543-4.551, three from 8 stages 4.509-4.524 (vit_linear_dgrad
+              // 0.784 -> 0.728, vit_linear_fwd 0.774 -> 0.741, conv_fwd 0.410 -> 0.388 ms/step)
+              if (kps / 64 >= 8 && (!CONV_A || ep.stats || ep.rowadd)) {
                 hipLaunchKernelGGL((gemm_kernel<T, BMc, BNc, LA, LB, EKc, false, 3>), g, dim3(GEMM_THREADS), 0, st,
                                    la, lb, M, N, K, kps, ep);
                 return;

@@ -99,16 +99,9 @@ int check_epi(const hvit_epilogue_t* e) {
 // choose split-K so that a wgrad launch has enough workgroups: about 256
 // workgroups of the given tile (one per CU, two for 64x64 tiles; each keeps
 // >= 4 K-stages)
-// (conv: the implicit-im2col weight gradient, whose 128x64 tiles fit more
-// workgroups per CU; HVIT_WG_TARGET / HVIT_CONV_WG_TARGET override the targets
-// for A/B measurements only)
-// wg_target: the caller's workgroup target for the linear weight gradients
-// that follow (hvit_set_wgrad_target; 0 = the default above) -- the side-stream
-// weight gradients, which share the chip with the data-gradient chain
-long wg_target = 0;
-int wgrad_splits(long M, long N, long K, int bm, int bn, int bk = 64, bool conv = false) {
+int wgrad_splits(long M, long N, long K, int bm, int bn, int bk = 64) {
   long tiles = (long)cdiv(M, bm) * cdiv(N, bn);
-  const long target = bm * bn <= 64 * 64 ? 512 : conv ? 256 : wg_target > 0 ? wg_target : 256;
+  const long target = bm * bn <= 64 * 64 ? 512 : 256;
   long want = (target + tiles - 1) / tiles;
   long maxs = K / (4 * bk);
   // a multiple of 8 slices: with the XCD-aware tile order (gemm.h tile_of)
@@ -126,7 +119,7 @@ int wgrad_splits(long M, long N, long K, int bm, int bn, int bk = 64, bool conv 
 // near 1) with >= 1.5 workgroups per CU on average for latency hiding, and
 // prefer fewer splits (less slab traffic).  Measured on enc1 (9 tiles,
 // tools/wgrad_sweep.py, B=32): 288 WGs 226 us, 432 -> 169, 576 -> 203,
-// 792 -> 185.  HVIT_CONV_WG_TARGET selects the older fixed-target rule (A/B).
+// 792 -> 185.
 int conv_wgrad_splits(int M, long N, long K, int bm, int bn, int bk = 64) {
   const long tiles = (long)cdiv(M, bm) * cdiv(N, bn);
   const long maxs = std::max(1L, std::min(256L, K / (4 * bk)));
@@ -245,6 +238,13 @@ bool thin_o1(const hvit_conv_geom_t* g) {
 }
 
 }  // namespace
+
+// C[M][N] = sum_k A[m][k] B[k][n] on gemm.h's kernels: A rows K-contiguous, B
+// [K][N] (the linear and the patch-embedding data gradients; gemm_linear.hip
+// holds the one instantiation).  bad_align is the error text when N or K is
+// not a multiple of 16 bytes of dt.
+int hvit_gemm_kc_mn(int dt, const void* a, const void* b, int M, int N, int K, const Epi& ep, hipStream_t st,
+                    const char* bad_align);
 
 int hvit_thin_c1_fwd(int dt, const hvit_conv_geom_t* g, const void* w, void* y, int y_dt, float* stats, hipStream_t st);
 // split-K slabs a conv weight gradient left for its caller to reduce

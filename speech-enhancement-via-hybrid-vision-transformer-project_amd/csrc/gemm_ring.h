@@ -301,18 +301,17 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NB == 2) ? (BN == 64
 }
 
 // ---------------------------------------------------------------- host -----
-// Ring configurations (HVIT_RING selects one for A/B; 0 = the gemm.h path):
-//   1: 128x128, 4 waves (2x2), 4-stage ring (128 KiB, one workgroup per CU)
-//   2: 128x128, 4 waves, 2-stage ring (64 KiB, two workgroups per CU)
-//   3: 256x128, 8 waves (4x2), 3-stage ring (144 KiB)
+// Ring configurations (hvit_ring_tune selects one; 0 = the gemm.h path):
+//   2: 128x128, 4 waves (2x2), 2-stage ring (64 KiB, two workgroups per CU)
 //   4: 256x256, 8 waves (2x4), 2-stage ring (128 KiB)
 //   5: 128x64, 4 waves (2x2), 2-stage ring (48 KiB, three workgroups per CU)
+// (1, a 4-stage 128x128 ring, and 3, a 3-stage 256x128 one, won at no shape
+// -- profiles/r5_ring_cfg_sweep.txt; the numbers are not reused)
 struct RingCfg {
   int bm, bn;
 };
 inline RingCfg ring_cfg(int c) {
   switch (c) {
-    case 3: return {256, 128};
     case 4: return {256, 256};
     case 5: return {128, 64};
     default: return {128, 128};
@@ -325,14 +324,6 @@ int launch_ring(int cfg, const LdDense<bf16_t, KCA>& la, const LdDense<bf16_t, K
   const RingCfg rc = ring_cfg(cfg);
   dim3 g(M / rc.bm, N / rc.bn, splits);
   switch (cfg) {
-    case 2:
-      hipLaunchKernelGGL((gemm_ring_kernel<128, 128, 2, 2, 2, KCA, KCB, EK>), g, dim3(256), 0, st, la, lb, M, N, K,
-                         kps, ep);
-      break;
-    case 3:
-      hipLaunchKernelGGL((gemm_ring_kernel<256, 128, 4, 2, 3, KCA, KCB, EK>), g, dim3(512), 0, st, la, lb, M, N, K,
-                         kps, ep);
-      break;
     case 4:
       hipLaunchKernelGGL((gemm_ring_kernel<256, 256, 2, 4, 2, KCA, KCB, EK>), g, dim3(512), 0, st, la, lb, M, N, K,
                          kps, ep);
@@ -341,8 +332,8 @@ int launch_ring(int cfg, const LdDense<bf16_t, KCA>& la, const LdDense<bf16_t, K
       hipLaunchKernelGGL((gemm_ring_kernel<128, 64, 2, 2, 2, KCA, KCB, EK>), g, dim3(256), 0, st, la, lb, M, N, K,
                          kps, ep);
       break;
-    default:
-      hipLaunchKernelGGL((gemm_ring_kernel<128, 128, 2, 2, 4, KCA, KCB, EK>), g, dim3(256), 0, st, la, lb, M, N, K,
+    default:  // 2
+      hipLaunchKernelGGL((gemm_ring_kernel<128, 128, 2, 2, 2, KCA, KCB, EK>), g, dim3(256), 0, st, la, lb, M, N, K,
                          kps, ep);
       break;
   }
@@ -369,7 +360,7 @@ bool ring_ok(int cfg, const LdDense<bf16_t, KCA>& la, const LdDense<bf16_t, KCB>
   return dense_bytes(la) < (1L << 31) && dense_bytes(lb) < (1L << 31);
 }
 
-// the configuration the linear entry points use (-1 automatic; hvit_gemm_tune
+// the configuration the linear entry points use (-1 automatic; hvit_ring_tune
 // for in-process A/B measurements and the tests)
 inline int& ring_cfg_ref() {
   static int c = -1;

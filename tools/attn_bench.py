@@ -67,7 +67,7 @@ def main(p=0.1, N=256):
 
 def fp8_main(p=0.1, N=256):
     """config 5's attention (B=16, N=256, H=12, hd=64; N < 256: the partial-tile forms): the bf16 forward against
-    the fp8 forms (hvit_gemm_tune(5, form): 0 round-4 kernel, 1 v2 16 waves,
+    the fp8 forms (hvit_gemm_tune(L.TUNE_FP8_FWD, form): 0 round-4 kernel, 1 v2 16 waves,
     2 v2 8 waves), keep-bit entry points (the training path)."""
     B, H, hd = 16, 12, 64
     D = H * hd
@@ -84,14 +84,14 @@ def fp8_main(p=0.1, N=256):
     print(f"N={N} config5 bf16 fwd_kb p={p}: {us:7.1f} us  {fl / us / 1e6:6.1f} TF/s", flush=True)
     f8 = lambda: L.call("hvit_mhsa_fwd_fp8_kb", qkv.data_ptr(), B, N, H, hd, hd ** -0.5, dr,  # noqa
                         o.data_ptr(), lse.data_ptr(), kb.data_ptr(), st())
-    old = L.lib().hvit_gemm_tune(5, 1)
+    old = L.lib().hvit_gemm_tune(L.TUNE_FP8_FWD, 1)
     try:
         for form in (0, 1, 2):
-            L.lib().hvit_gemm_tune(5, form)
+            L.lib().hvit_gemm_tune(L.TUNE_FP8_FWD, form)
             us = timeit(f8)
             print(f"N={N} config5 fp8 form {form} fwd_kb p={p}: {us:7.1f} us  {fl / us / 1e6:6.1f} TF/s", flush=True)
     finally:
-        L.lib().hvit_gemm_tune(5, old)
+        L.lib().hvit_gemm_tune(L.TUNE_FP8_FWD, old)
 
 
 if __name__ == "__main__":

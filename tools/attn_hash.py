@@ -78,10 +78,10 @@ def run_fp8(B, N, H, p):
     hd, D = 64, H * 64
     qkv, _ = inputs(L.BF16, B, N, H, hd, 8000 + N)
     dr = L.dropout(p, 77, 23) if p > 0 else None
-    old = lib.hvit_gemm_tune(5, 1)
+    old = lib.hvit_gemm_tune(L.TUNE_FP8_FWD, 1)
     try:
         for form in (0, 1, 2):
-            lib.hvit_gemm_tune(5, form)
+            lib.hvit_gemm_tune(L.TUNE_FP8_FWD, form)
             for with_kb in (False, True):
                 o = torch.zeros(B * N, D, device=DEV, dtype=torch.bfloat16)
                 lse = torch.zeros(B, H, N, device=DEV)
@@ -90,7 +90,7 @@ def run_fp8(B, N, H, p):
                        lse.data_ptr(), kb.data_ptr() if with_kb else None, st())
                 emit(f"fp8 N={N} p={p} form={form} kb={int(with_kb)}", o=o, lse=lse, bits=kb)
     finally:
-        lib.hvit_gemm_tune(5, old)
+        lib.hvit_gemm_tune(L.TUNE_FP8_FWD, old)
 
 
 def main():
@@ -98,12 +98,12 @@ def main():
     B, H = 2, 2
     for N in (16, 36, 100, 228, 240, 256, 300, 496, 512):
         for p in (0.0, 0.3):
-            for fused in ((0, 1) if N <= 256 else (1,)):  # hvit_gemm_tune(4, .): kernel pair / single pass
-                old = lib.hvit_gemm_tune(4, fused)
+            for fused in ((0, 1) if N <= 256 else (1,)):  # hvit_gemm_tune(L.TUNE_ATTN_BWD, .): kernel pair / single pass
+                old = lib.hvit_gemm_tune(L.TUNE_ATTN_BWD, fused)
                 try:
                     run(f"bf16 hd=64 N={N} p={p} tune4={fused}", L.BF16, B, N, H, 64, p)
                 finally:
-                    lib.hvit_gemm_tune(4, old)
+                    lib.hvit_gemm_tune(L.TUNE_ATTN_BWD, old)
     # the generic kernels
     for p in (0.0, 0.3):
         run(f"generic bf16 hd=64 N=520 p={p}", L.BF16, B, 520, H, 64, p)

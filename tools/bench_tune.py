@@ -1,7 +1,8 @@
 """bench.py with library tuning knobs set first (same-process A/B of a
 hvit_gemm_tune form or a functional.py path switch):
-    python tools/bench_tune.py 6=1 HF.WGRAD_GROUP=0 -- --no-cpu-baseline
-(``what=value`` / ``HF.NAME=int`` before ``--``, bench.py's arguments after)."""
+    python tools/bench_tune.py 9=0 HF.WGRAD_GROUP=0 -- --no-cpu-baseline
+(``what=value``, what a HVIT_TUNE_* number of include/hvit.h, / ``HF.NAME=int`` before ``--``, bench.py's
+arguments after)."""
 
 import os
 import sys

@@ -1,10 +1,11 @@
 """Backward of one ViT linear (B=32 x 256 tokens, bf16): how long the data
 gradient and the weight gradient take alone, back to back (the step's form:
 the weight gradient's split-K slab sum carried by the data-gradient launch), and
-concurrently on two streams, for several split-K workgroup targets of the
-weight gradient.  HIP events on the launching stream around each form.
+concurrently on two streams.  HIP events on the launching stream around each
+form.  (The sweep over split-K workgroup targets of the weight gradient is
+recorded in profiles/r6_bwd_pair_probe.txt; its knob went with the measurement.)
 
-    python tools/bwd_pair_probe.py [reps=20] [targets=0,128,64]
+    python tools/bwd_pair_probe.py [reps=20]
 """
 
 import os
@@ -72,9 +73,8 @@ def linears():
 def main():
     args = dict(a.split("=") for a in sys.argv[1:])
     reps = int(args.get("reps", "20"))
-    targets = [int(t) for t in args.get("targets", "0,128,64").split(",")]
     s2 = torch.cuda.Stream()
-    print(f"{'linear':6s} {'target':>6s} {'dgrad':>8s} {'wgrad+sum':>10s} {'seq(step)':>10s} {'conc w|d':>9s} "
+    print(f"{'linear':6s} {'dgrad':>8s} {'wgrad+sum':>10s} {'seq(step)':>10s} {'conc w|d':>9s} "
           f"{'conc d|w':>9s}  GFLOP  TF/s(seq) TF/s(best)")
     for name, dy, W, x, epi, odt, K in linears():
         N = dy.shape[1]
@@ -109,17 +109,14 @@ def main():
                 s1.wait_stream(s2)
             return f
 
-        for t in targets:
-            old = L.lib().hvit_gemm_tune(2, t)
-            td = timeit(dgrad, reps)
-            tw = timeit(wgrad_now, reps)
-            ts = timeit(seq, reps)
-            tc1 = timeit(conc(True), reps)
-            tc2 = timeit(conc(False), reps)
-            L.lib().hvit_gemm_tune(2, old)
-            best = min(ts, tc1, tc2)
-            print(f"{name:6s} {t:6d} {td:8.1f} {tw:10.1f} {ts:10.1f} {tc1:9.1f} {tc2:9.1f}  {gf:5.1f} "
-                  f"{gf / ts * 1e3:9.0f} {gf / best * 1e3:9.0f}", flush=True)
+        td = timeit(dgrad, reps)
+        tw = timeit(wgrad_now, reps)
+        ts = timeit(seq, reps)
+        tc1 = timeit(conc(True), reps)
+        tc2 = timeit(conc(False), reps)
+        best = min(ts, tc1, tc2)
+        print(f"{name:6s} {td:8.1f} {tw:10.1f} {ts:10.1f} {tc1:9.1f} {tc2:9.1f}  {gf:5.1f} "
+              f"{gf / ts * 1e3:9.0f} {gf / best * 1e3:9.0f}", flush=True)
 
 
 if __name__ == "__main__":

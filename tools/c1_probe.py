@@ -16,7 +16,7 @@ L = hv._lib
 HF = sys.modules["hvit_amd.functional"]
 args = dict(a.split("=") for a in sys.argv[1:])
 reps = int(args.get("reps", 20))
-L.lib().hvit_gemm_tune(1, int(args.get("mfma", 1)))
+L.lib().hvit_gemm_tune(L.TUNE_C1_MFMA, int(args.get("mfma", 1)))
 N, H, W, C, P = int(args.get("n", 32)), 256, 256, 64, 2
 dev = "cuda"
 x = torch.rand(N, H, W, 1, device=dev).to(torch.bfloat16)

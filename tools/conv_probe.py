@@ -55,22 +55,22 @@ def main():
         tr = L.lib().hvit_conv_bn_tile_rows(g)
         part = torch.empty(((P + tr - 1) // tr, Cout, 2), device=dev)
         fl = 2.0 * P * Cout * (C1 + C2) * KS * KS
-        # halo-resident A operand off / wherever it applies (hvit_gemm_tune(9, v); bit-identical results)
+        # halo-resident A operand off / wherever it applies (hvit_gemm_tune(L.TUNE_CONV_HALO, v); bit-identical results)
         halo = {}
         for v in (0, 2):
-            old = L.lib().hvit_gemm_tune(9, v)
-            n0 = L.lib().hvit_gemm_tune(10, 0)
+            old = L.lib().hvit_gemm_tune(L.TUNE_CONV_HALO, v)
+            n0 = L.lib().hvit_gemm_tune(L.TUNE_CONV_HALO_COUNT, 0)
             tb = timeit(lambda: L.call("hvit_conv_fwd", L.BF16, g, wp.data_ptr(), None, z.data_ptr(), L.BF16,
                                        part.data_ptr(), None, s()))
-            nf = L.lib().hvit_gemm_tune(10, 0) - n0
+            nf = L.lib().hvit_gemm_tune(L.TUNE_CONV_HALO_COUNT, 0) - n0
             wd_ = HF.pack_conv(w, 1, L.BF16)
             dz_ = torch.randn(B, Ho, Wo, Cout, device=dev).to(torch.bfloat16)
             dx_ = torch.empty(B, Ho, Wo, C1 + C2, device=dev, dtype=torch.bfloat16)
-            n0 = L.lib().hvit_gemm_tune(10, 0)
+            n0 = L.lib().hvit_gemm_tune(L.TUNE_CONV_HALO_COUNT, 0)
             td = timeit(lambda: L.call("hvit_conv_dgrad", L.BF16, g, dz_.data_ptr(), wd_.data_ptr(), dx_.data_ptr(),
                                        L.BF16, s()))
-            nd = L.lib().hvit_gemm_tune(10, 0) - n0
-            L.lib().hvit_gemm_tune(9, old)
+            nd = L.lib().hvit_gemm_tune(L.TUNE_CONV_HALO_COUNT, 0) - n0
+            L.lib().hvit_gemm_tune(L.TUNE_CONV_HALO, old)
             halo[v] = (tb, nf > 0, td, nd > 0)
         print(f"{name:5s} tune9=0 fwd+bn {halo[0][0]:7.1f} us dgrad {halo[0][2]:7.1f} us | tune9=2 fwd+bn "
               f"{halo[2][0]:7.1f} us ({'halo' if halo[2][1] else 'per-tap'}) dgrad {halo[2][2]:7.1f} us "

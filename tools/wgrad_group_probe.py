@@ -28,9 +28,9 @@ def main():
     M = int(args.get("M", "8192"))
     D = int(args.get("D", "512"))
     reps = int(args.get("reps", "20"))
-    cfg = int(args.get("cfg", "0"))  # hvit_gemm_tune(7, cfg): tile configuration
+    cfg = int(args.get("cfg", "0"))  # hvit_gemm_tune(L.TUNE_WGRAD_GROUP, cfg): tile configuration
     same = int(args.get("same", "0"))  # 1: every block's problems read the same operands (L2-resident ceiling)
-    L.lib().hvit_gemm_tune(7, cfg)
+    L.lib().hvit_gemm_tune(L.TUNE_WGRAD_GROUP, cfg)
     hid = 4 * D
     g = torch.Generator(device=DEV).manual_seed(0)
     keep, probs, flops = [], [], 0.0

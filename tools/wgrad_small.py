@@ -1,7 +1,6 @@
 """Isolated timing of the small weight gradients of the B=32 step (head
 to_feature_map and the three skip projections, bias included):
-dW[N, K] = dy^T x, db = colsum(dy) over tall M.  Env knobs of the library
-(HVIT_NO_RS, HVIT_RING, ...) select the variant for A/B runs."""
+dW[N, K] = dy^T x, db = colsum(dy) over tall M."""
 import os
 import sys
 

@@ -1,10 +1,8 @@
 """Time hvit_conv_wgrad on every conv of the default model at B=32 (bf16),
 one line per conv: average microseconds over a loop of launches, measured with
-HIP events on the current stream.  Planner variants are selected by the
-environment of the calling process (e.g. HVIT_CONV_WG_TARGET), so a sweep runs
-this once per setting:
+HIP events on the current stream.
 
-    for t in 256 384 512; do HVIT_CONV_WG_TARGET=$t python tools/wgrad_sweep.py; done
+    python tools/wgrad_sweep.py
 """
 
 import os
@@ -60,7 +58,7 @@ def main(reps=30):
         flop = 2.0 * B * Ho * Wo * Cout * (C1 + C2) * KS * KS
         tot += us
         print(f"{name:6s} {us:8.1f} us  {flop / us / 1e6:7.1f} TFLOP/s", flush=True)
-    print(f"total  {tot:8.1f} us  [{os.environ.get('HVIT_CONV_WG_TARGET', '-')}]", flush=True)
+    print(f"total  {tot:8.1f} us", flush=True)
 
 
 if __name__ == "__main__":
