@@ -581,6 +581,58 @@ long long hvit_lsd_ws_elems(int B, int T);
 int hvit_lsd(const float* mag_a, const float* mag_b, const int* lengths, int B, int F, int T, int hop, double eps,
              double* ws, long long ws_elems, double* out, void* stream);
 
+/* Training batches assembled on the device: the reference's cached
+ * __getitem__ (data/dataset.py:233-294), SpectrogramAugmenter.augment on the
+ * noisy side (data/augmentation.py:48-118) and collate_fn's right padding
+ * (data/dataset.py:297-347) in one launch.
+ *
+ * noisy_store / clean_store are packed f32 stores: utterance i is [F, T_i]
+ * row-major (row stride T_i, no padding) at element offsets[i] of both, T_i =
+ * frames[i]; offsets (int64 [n_utts]) and frames (int32 [n_utts]) are device
+ * arrays.  idx (int32 device [B], repeats allowed) selects the batch; an index
+ * outside 0 .. n_utts - 1 is clamped into it.  Tb is the padded frame count and
+ * max_frames the largest selected T_i, both known to the host that built the
+ * store: Tb < max_frames is an error (and a stored T_i above Tb is cut at Tb,
+ * so nothing is ever written outside the outputs).
+ *
+ * clean [B, 1, F, Tb]: row b is the stored utterance idx[b], bit for bit,
+ *   followed by zeros for t >= T_b.
+ * noisy [B, 1, F, Tb]: the same from the noisy store; with cfg->enabled, first
+ *   freq_mask_num times rows f0 <= r < f0 + f set to 0 with f = randint(0,
+ *   freq_mask_width), f0 = randint(0, max(1, F - f)) (augmentation.py:89-92),
+ *   then time_mask_num times frames t0 <= s < t0 + t set to 0 with t =
+ *   randint(0, min(time_mask_width, T_b)), t0 = randint(0, max(1, T_b - t))
+ *   on the sample's own T_b (:95-98), masks ending at the array edge as a
+ *   slice assignment does; then, with probability gain_prob (:63), every
+ *   element times 10^(dB / 20), dB uniform in [gain_db_lo, gain_db_hi)
+ *   (:115-118), one f32 multiply, no clipping.  Masked and padded elements are
+ *   not read from the store.
+ * plan (int32 [B, 2 * freq_mask_num + 2 * time_mask_num + 2]): what row b
+ *   used: (f0, f) per frequency mask, (t0, t) per time mask, 1 if the gain was
+ *   drawn, the f32 bits of the gain (1.0 when not drawn).  Disabled: zeros and
+ *   gain 1.0, and noisy is the plain gather and pad.
+ *
+ * Draws: u32(b, j) = hash32(rng_key(*seed_ptr, 0xBA7C) ^ (64 b + j)) for the
+ * sample's j-th draw in the order above (f, f0 per mask; t, t0 per mask; the
+ * gain's Bernoulli; its dB), a stateless function of (*seed_ptr, b, j):
+ * randint(0, n) = (u32 * n) >> 32; the gain is drawn iff u32 < floor(gain_prob
+ * * 2^32) (always for gain_prob >= 1); dB = lo + (hi - lo) * ((u32 >> 8) *
+ * 2^-24), each operation rounded to f32.  seed_ptr is the word hvit_rng_advance
+ * wrote for this batch (required when enabled), so a captured launch draws new
+ * masks on every replay.  No host sync, no allocation, no atomics; a mask
+ * count above 0 with a width below 1 is an error (numpy's randint(0, 0)
+ * raises), as are B < 1 and null pointers. */
+#define HVIT_AUG_MAX_MASKS 8 /* freq_mask_num and time_mask_num are at most this */
+typedef struct {
+  int enabled;
+  int freq_mask_num, freq_mask_width;
+  int time_mask_num, time_mask_width;
+  float gain_prob, gain_db_lo, gain_db_hi;
+} hvit_augment_cfg_t;
+int hvit_batch_prep(const float* noisy_store, const float* clean_store, const long long* offsets, const int* frames,
+                    int n_utts, const int* idx, int B, int F, int Tb, int max_frames, const hvit_augment_cfg_t* cfg,
+                    const unsigned long long* seed_ptr, float* noisy, float* clean, int* plan, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

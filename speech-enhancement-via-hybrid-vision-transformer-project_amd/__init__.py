@@ -11,7 +11,10 @@ plus the factory it forgot to export):
     stft_mag / istft_mag / supported / n_frames (the device STFT / iSTFT front end, frontend.py),
     compute_sisdr / compute_snr / compute_segsnr / compute_lsd / compute_pesq / compute_stoi /
     compute_all_metrics / print_metrics (evaluation/metrics.py on the host), wave_metrics / lsd /
-    all_metrics_batch (the same scores on GPU batches, metrics.py) and Evaluator (evaluation/evaluator.py)
+    all_metrics_batch (the same scores on GPU batches, metrics.py) and Evaluator (evaluation/evaluator.py),
+    SpectrogramAugmenter / plan_host / apply_plan_host (data/augmentation.py drawn on the device, augment.py),
+    SpectrogramStore / DeviceBatchLoader (the dataset cached on the GPU and its loader, data.py),
+    create_scheduler / WarmupCosineScheduler (training/optimizer.py:76-200) and Trainer (training/trainer.py)
 """
 
 from .hybrid_vit import (  # noqa: F401
@@ -28,7 +31,13 @@ from .hybrid_vit import (  # noqa: F401
     create_hybrid_vit,
 )
 from .losses import CombinedLoss, create_loss_function  # noqa: F401
-from .optim import FusedAdamW, clip_grad_norm_, create_optimizer  # noqa: F401
+from .optim import (  # noqa: F401
+    FusedAdamW,
+    WarmupCosineScheduler,
+    clip_grad_norm_,
+    create_optimizer,
+    create_scheduler,
+)
 from .train_step import GraphedTrainStep  # noqa: F401
 from .config import load_all_configs, load_config, merge_configs  # noqa: F401
 from .frontend import istft_mag, n_frames, stft_mag, supported  # noqa: F401
@@ -46,6 +55,9 @@ from .metrics import (  # noqa: F401
     wave_metrics,
 )
 from .evaluator import Evaluator  # noqa: F401
+from .augment import SpectrogramAugmenter, apply_plan_host, plan_host  # noqa: F401
+from .data import DeviceBatchLoader, SpectrogramStore  # noqa: F401
+from .trainer import Trainer  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = [
@@ -55,4 +67,6 @@ __all__ = [
     "load_all_configs", "load_config", "merge_configs", "stft_mag", "istft_mag", "supported", "n_frames",
     "compute_sisdr", "compute_snr", "compute_segsnr", "compute_lsd", "compute_pesq", "compute_stoi",
     "compute_all_metrics", "print_metrics", "wave_metrics", "lsd", "all_metrics_batch", "Evaluator",
+    "SpectrogramAugmenter", "plan_host", "apply_plan_host", "SpectrogramStore", "DeviceBatchLoader",
+    "create_scheduler", "WarmupCosineScheduler", "Trainer",
 ]

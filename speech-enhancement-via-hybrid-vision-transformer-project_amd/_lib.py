@@ -89,6 +89,14 @@ class AdamWHyper(C.Structure):
                 ("bc2", f32)]
 
 
+class AugmentCfg(C.Structure):
+    """hvit_augment_cfg_t: the batch-preparation launch's augmentation settings."""
+    _fields_ = [("enabled", i32), ("freq_mask_num", i32), ("freq_mask_width", i32), ("time_mask_num", i32),
+                ("time_mask_width", i32), ("gain_prob", f32), ("gain_db_lo", f32), ("gain_db_hi", f32)]
+
+
+AUG_MAX_MASKS = 8  # include/hvit.h: HVIT_AUG_MAX_MASKS
+
 P = C.POINTER
 _SIGS = {
     "hvit_last_error": ([], C.c_char_p),
@@ -175,6 +183,7 @@ _SIGS = {
     "hvit_wave_metrics": ([vp, i64, vp, i64, vp, i32, i32, i32, i32, f64, vp, i64, vp, vp], i32),
     "hvit_lsd_ws_elems": ([i32, i32], i64),
     "hvit_lsd": ([vp, vp, vp, i32, i32, i32, i32, f64, vp, i64, vp, vp], i32),
+    "hvit_batch_prep": ([vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, P(AugmentCfg), vp, vp, vp, vp, vp], i32),
 }
 
 EXPORTED = sorted(k for k in _SIGS)

@@ -261,3 +261,68 @@ def create_optimizer(model: torch.nn.Module, config: Dict[str, Any]) -> torch.op
         return torch.optim.SGD(model.parameters(), lr=lr, momentum=oc.get("momentum", 0.9), weight_decay=wd,
                                nesterov=oc.get("nesterov", True))
     raise ValueError(f"Unknown optimizer: {name}")
+
+
+class WarmupCosineScheduler:
+    """training/optimizer.py:136-198: linear warm-up over ``warmup_epochs``
+    (scale (epoch + 1) / warmup_epochs), then cosine annealing of the scale
+    from 1 to ``eta_min`` (:187-190: eta_min scales the base rate there, it is
+    not an absolute rate).  ``step()`` advances the epoch first, as the
+    reference does, so the rates of epoch 0 are the optimizer's own.  Adds the
+    ``state_dict`` / ``load_state_dict`` that Trainer.save_checkpoint calls
+    (trainer.py:369-370) and the reference class lacks."""
+
+    def __init__(self, optimizer: torch.optim.Optimizer, warmup_epochs: int, max_epochs: int, eta_min: float = 0.0):
+        self.optimizer = optimizer
+        self.warmup_epochs = warmup_epochs
+        self.max_epochs = max_epochs
+        self.eta_min = eta_min
+        self.base_lrs = [g["lr"] for g in optimizer.param_groups]
+        self.current_epoch = 0
+
+    def step(self, epoch: Optional[int] = None) -> None:
+        import math
+
+        self.current_epoch = epoch if epoch is not None else self.current_epoch + 1
+        if self.current_epoch < self.warmup_epochs:
+            scale = (self.current_epoch + 1) / self.warmup_epochs
+        else:
+            progress = (self.current_epoch - self.warmup_epochs) / (self.max_epochs - self.warmup_epochs)
+            scale = self.eta_min + (1.0 - self.eta_min) * 0.5 * (1.0 + math.cos(math.pi * progress))
+        for g, base in zip(self.optimizer.param_groups, self.base_lrs):
+            g["lr"] = base * scale
+
+    def get_last_lr(self):
+        return [g["lr"] for g in self.optimizer.param_groups]
+
+    def state_dict(self) -> Dict[str, Any]:
+        return {"warmup_epochs": self.warmup_epochs, "max_epochs": self.max_epochs, "eta_min": self.eta_min,
+                "base_lrs": list(self.base_lrs), "current_epoch": self.current_epoch}
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        for k in ("warmup_epochs", "max_epochs", "eta_min", "base_lrs", "current_epoch"):
+            setattr(self, k, sd[k])
+
+
+def create_scheduler(optimizer: torch.optim.Optimizer, config: Dict[str, Any]):
+    """training/optimizer.py:76-133: 'cosine' (default), 'warmup_cosine',
+    'step', 'plateau' or 'none' from ``config['scheduler']``, over
+    ``config['num_epochs']`` epochs."""
+    from torch.optim.lr_scheduler import CosineAnnealingLR, ReduceLROnPlateau, StepLR
+
+    sc = config.get("scheduler", {})
+    name = sc.get("name", "cosine").lower()
+    num_epochs = config.get("num_epochs", 100)
+    if name == "cosine":
+        return CosineAnnealingLR(optimizer, T_max=num_epochs, eta_min=sc.get("min_lr", 1e-6))
+    if name == "warmup_cosine":
+        return WarmupCosineScheduler(optimizer, warmup_epochs=sc.get("warmup_epochs", 5), max_epochs=num_epochs,
+                                     eta_min=sc.get("min_lr", 1e-6))
+    if name == "step":
+        return StepLR(optimizer, step_size=sc.get("step_size", 30), gamma=sc.get("gamma", 0.1))
+    if name == "plateau":
+        return ReduceLROnPlateau(optimizer, mode="min", factor=sc.get("factor", 0.5), patience=sc.get("patience", 5),
+                                 min_lr=sc.get("min_lr", 1e-6))
+    if name == "none":
+        return None
+    raise ValueError(f"Unknown scheduler: {name}")
