@@ -13,6 +13,8 @@
 // Window / pixel indices stay in 32 bits.
 #include <algorithm>
 
+#include "bn_tail.h"
+#include "chan_vec.h"
 #include "common.h"
 
 namespace hvit {
@@ -22,22 +24,9 @@ namespace hvit {
 // the sums grid is capped at BN_PART_ROWS
 constexpr int BN_PART_ROWS = 1024;
 
+// channels per 16-byte vector of T: the channel group one thread owns
 template <typename T>
-struct V16 {  // 16 bytes of T as floats
-  static constexpr int N = 16 / sizeof(T);
-  __device__ __forceinline__ static void load(const T* p, float* f) {
-    u32x4 u = *(const u32x4*)p;
-    const T* e = (const T*)&u;
-#pragma unroll
-    for (int i = 0; i < N; ++i) f[i] = Elem<T>::to_f(e[i]);
-  }
-  __device__ __forceinline__ static void store(T* p, const float* f) {
-    T e[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) e[i] = Elem<T>::from_f(f[i]);
-    *(u32x4*)p = *(const u32x4*)e;
-  }
-};
+constexpr int CV16 = 16 / sizeof(T);
 
 struct BnArgs {
   int N, H, W, C, pool;
@@ -45,48 +34,44 @@ struct BnArgs {
   const float* invstd;
   const float* gamma;
   const float* beta;
-  uint32_t thr;
-  float dscale;
-  uint32_t key;  // rng_key(seed, site) (host-resolved when seedp is NULL)
-  const unsigned long long* seedp;  // device seed word (hvit_dropout_t.seed_ptr)
-  unsigned long long seed;
-  uint32_t site;
+  DropKey drop;
   // index divisors: channel groups, full windows (Wo, Ho), all windows (Ww, Hw)
   FastDiv fG, fWo, fHo, fWw, fHw;
-  // at kernel entry: fold in the device seed word (one scalar load)
-  __device__ __forceinline__ void resolve() {
-    if (seedp && thr) key = rng_key(seed ^ *seedp, site);
-  }
 };
 
-// CV per-channel constants p[c .. c+CV-1] as 16-byte vector loads (c is a
-// multiple of CV): scalar loads of them came out serialised one round trip
-// each (48 of them in the apply pass), a ~20 us floor on every launch
+// sc, sh of channels c .. c+CV-1 (and mean, invstd for the backward's xhat).
+// The per-channel constants go as 16-byte vector loads (c is a multiple of
+// CV): scalar loads of them came out serialised one round trip each (48 of
+// them in the apply pass), a ~20 us floor on every launch
 template <int CV>
-__device__ __forceinline__ void load_cv(const float* __restrict__ p, int c, float* out) {
+__device__ __forceinline__ void bn_consts(const BnArgs& a, int c, float* sc, float* sh, float* mu, float* is) {
+  float ga[CV], be[CV];
+  load_chan<CV>(a.mean + c, mu);
+  load_chan<CV>(a.invstd + c, is);
+  load_chan<CV>(a.gamma + c, ga);
+  load_chan<CV>(a.beta + c, be);
 #pragma unroll
-  for (int v = 0; v < CV / 4; ++v) {
-    const f32x4 x = *(const f32x4*)(p + c + 4 * v);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) out[4 * v + e] = x[e];
-  }
+  for (int e = 0; e < CV; ++e) bn_scale_shift(mu[e], is[e], ga[e], be[e], sc[e], sh[e]);
 }
 
-// Dropout2d multipliers of channels c .. c+CV-1 of sample n (element index
-// n*C + c, a multiple of 4: two pair hashes per four channels)
-template <int CV>
-__device__ __forceinline__ void drop_mask(const BnArgs& a, int n, int c, float* m) {
-  if (!a.thr) {
+// CV values of y / dy, whose dtype need not be z's: one 16-byte vector when
+// the element sizes match, else element by element
+template <int CV, typename TD>
+__device__ __forceinline__ void load_io(const TD* p, float* f) {
+  if constexpr (CV * sizeof(TD) == 16) {
+    load_chan<CV>(p, f);
+  } else {
 #pragma unroll
-    for (int e = 0; e < CV; ++e) m[e] = 1.f;
-    return;
+    for (int e = 0; e < CV; ++e) f[e] = Elem<TD>::to_f(p[e]);
   }
-  const uint64_t i0 = (uint64_t)n * a.C + c;
+}
+template <int CV, typename TO>
+__device__ __forceinline__ void store_io(TO* p, const float* f) {
+  if constexpr (CV * sizeof(TO) == 16) {
+    store_chan<CV>(p, f);
+  } else {
 #pragma unroll
-  for (int e4 = 0; e4 < CV; e4 += 4) {
-    const f32x4 k = keep4_at(a.key, i0 + e4, a.thr, a.dscale);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) m[e4 + e] = k[e];
+    for (int e = 0; e < CV; ++e) p[e] = Elem<TO>::from_f(f[e]);
   }
 }
 
@@ -94,23 +79,15 @@ __device__ __forceinline__ void drop_mask(const BnArgs& a, int n, int c, float* 
 template <typename T, typename TO>
 __global__ __launch_bounds__(256) void bnact_fwd_kernel(const T* __restrict__ z, TO* __restrict__ y, BnArgs a_) {
   BnArgs a = a_;
-  a.resolve();
-  constexpr int CV = V16<T>::N;
+  a.drop.resolve();
+  constexpr int CV = CV16<T>;
   const int G = a.C / CV;
   const int Ho = a.H / a.pool, Wo = a.W / a.pool;
   const int total = a.N * Ho * Wo * G;
   // a thread's channel group never changes (256 % G == 0, grid stride % G == 0)
   const int c = ((blockIdx.x * blockDim.x + threadIdx.x) % G) * CV;
-  float sc[CV], sh[CV], mu_[CV], is_[CV], ga_[CV], be_[CV];
-  load_cv<CV>(a.mean, c, mu_);
-  load_cv<CV>(a.invstd, c, is_);
-  load_cv<CV>(a.gamma, c, ga_);
-  load_cv<CV>(a.beta, c, be_);
-#pragma unroll
-  for (int e = 0; e < CV; ++e) {
-    sc[e] = is_[e] * ga_[e];
-    sh[e] = be_[e] - mu_[e] * sc[e];
-  }
+  float sc[CV], sh[CV], mu[CV], is[CV];
+  bn_consts<CV>(a, c, sc, sh, mu, is);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int t = a.fG.div(i);
     const int t1 = a.fWo.div(t);
@@ -123,70 +100,45 @@ __global__ __launch_bounds__(256) void bnact_fwd_kernel(const T* __restrict__ z,
     for (int dy = 0; dy < a.pool; ++dy)
       for (int dx = 0; dx < a.pool; ++dx) {
         float v[CV];
-        V16<T>::load(z + ((size_t)(n * a.H + oy * a.pool + dy) * a.W + ox * a.pool + dx) * a.C + c, v);
+        load_chan<CV>(z + ((size_t)(n * a.H + oy * a.pool + dy) * a.W + ox * a.pool + dx) * a.C + c, v);
 #pragma unroll
         for (int e = 0; e < CV; ++e) best[e] = fmaxf(best[e], __builtin_fmaf(v[e], sc[e], sh[e]));
       }
     float m[CV];
-    drop_mask<CV>(a, n, c, m);
+    chan_keep<CV>(a.drop, n, a.C, c, m);
     float o[CV];
 #pragma unroll
     for (int e = 0; e < CV; ++e) o[e] = best[e] * m[e];
-    TO* dst = y + ((size_t)(n * Ho + oy) * Wo + ox) * a.C + c;
-    if constexpr (sizeof(TO) == sizeof(T)) {
-      V16<TO>::store(dst, o);
-    } else {
-#pragma unroll
-      for (int e = 0; e < CV; ++e) dst[e] = Elem<TO>::from_f(o[e]);
-    }
+    store_io<CV>(y + ((size_t)(n * Ho + oy) * Wo + ox) * a.C + c, o);
   }
 }
 
-// backward: APPLY = false -> per-channel sums; APPLY = true -> dz.  The
-// window values are formed with one explicit fma each (forward, reduce and
-// apply alike): equal inputs must give equal values so that a tie routes to
-// the first maximum, as torch's max-pool does (compiler-chosen contraction
-// made tied bf16 inputs differ by an ulp and move the gradient)
-template <typename T, typename TD, bool APPLY>
+// backward apply pass: dz of every pixel from the routed gradient (the first
+// maximum of its window, route_first_max; positions outside full windows get
+// none) and, in training mode, the sums of bnact_sums_kernel
+template <typename T, typename TD>
 __global__ __launch_bounds__(256) void bnact_bwd_kernel(const T* __restrict__ z, const TD* __restrict__ dy,
-                                                       BnArgs a_, float* __restrict__ sums, int training,
+                                                       BnArgs a_, const float* __restrict__ sums, int training,
                                                        T* __restrict__ dz) {
   BnArgs a = a_;
-  a.resolve();
-  constexpr int CV = V16<T>::N;
+  a.drop.resolve();
+  constexpr int CV = CV16<T>;
   constexpr int MAXW = 4;  // pool <= 2
-  __shared__ float red[2][256][CV];
   const int G = a.C / CV;
   const int P = a.pool;
   const int Ho = a.H / P, Wo = a.W / P;
   const int Hw = (a.H + P - 1) / P, Ww = (a.W + P - 1) / P;
   const int total = a.N * Hw * Ww * G;
   const float invM = 1.f / (float)(a.N * a.H * a.W);
-  float acc1[CV], acc2[CV];
-#pragma unroll
-  for (int e = 0; e < CV; ++e) acc1[e] = acc2[e] = 0.f;
   // a thread's channel group never changes (256 % G == 0, grid stride % G == 0):
   // per-channel constants are loaded once
   const int c = ((blockIdx.x * blockDim.x + threadIdx.x) % G) * CV;
-  // sc, sh: relu(bn(z)) = max(z*sc + sh, 0).  Reduce pass: xhat = (z - mu)*is.
-  // Apply pass (training): dz = sc*(g - s1 - xhat*s2) = sc*g + ca + cb*z.
-  float sc[CV], sh[CV], mu[CV], is[CV], ca[CV], cb[CV], ga_[CV], be_[CV], s1v[CV], s2v[CV];
-  load_cv<CV>(a.mean, c, mu);
-  load_cv<CV>(a.invstd, c, is);
-  load_cv<CV>(a.gamma, c, ga_);
-  load_cv<CV>(a.beta, c, be_);
-  load_cv<CV>(sums, c, s1v);        // (reduce pass: zeroed accumulators, unused)
-  load_cv<CV>(sums + a.C, c, s2v);
-  const bool use_s = APPLY && training;
+  float sc[CV], sh[CV], mu[CV], is[CV], ca[CV], cb[CV], s1v[CV], s2v[CV];
+  bn_consts<CV>(a, c, sc, sh, mu, is);
+  load_chan<CV>(sums + c, s1v);
+  load_chan<CV>(sums + a.C + c, s2v);
 #pragma unroll
-  for (int e = 0; e < CV; ++e) {
-    sc[e] = is[e] * ga_[e];
-    sh[e] = be_[e] - mu[e] * sc[e];
-    const float s1 = use_s ? s1v[e] * invM : 0.f;
-    const float s2 = use_s ? s2v[e] * invM : 0.f;
-    cb[e] = -sc[e] * s2 * is[e];
-    ca[e] = -sc[e] * s1 - cb[e] * mu[e];
-  }
+  for (int e = 0; e < CV; ++e) bn_bwd_coeffs(sc[e], mu[e], is[e], s1v[e], s2v[e], invM, training, ca[e], cb[e]);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int t = a.fG.div(i);
     const int t1 = a.fWw.div(t);
@@ -200,7 +152,7 @@ __global__ __launch_bounds__(256) void bnact_bwd_kernel(const T* __restrict__ z,
     for (int q = 0; q < MAXW; ++q) {
       const int y = wy * P + (q >> 1), x = wx * P + (q & 1);
       inb[q] = (q < P * P) && (P == 2 || q == 0) && y < a.H && x < a.W;
-      if (inb[q]) V16<T>::load(z + ((size_t)(n * a.H + y) * a.W + x) * a.C + c, zv[q]);
+      if (inb[q]) load_chan<CV>(z + ((size_t)(n * a.H + y) * a.W + x) * a.C + c, zv[q]);
     }
     const bool full = wy < Ho && wx < Wo;
     // routed gradient: gv[e] at window position arg[e] (first maximum), 0 elsewhere
@@ -211,84 +163,33 @@ __global__ __launch_bounds__(256) void bnact_bwd_kernel(const T* __restrict__ z,
       arg[e] = 0;
       gv[e] = 0.f;
     }
-    if (full) {
+    if (full) {  // (every position q < P * P of a full window is inside the image)
       float d[CV], m[CV];
-      const TD* dp = dy + ((size_t)(n * Ho + wy) * Wo + wx) * a.C + c;
-      if constexpr (sizeof(TD) == sizeof(T)) {
-        V16<TD>::load(dp, d);
-      } else {
-#pragma unroll
-        for (int e = 0; e < CV; ++e) d[e] = Elem<TD>::to_f(dp[e]);
-      }
-      drop_mask<CV>(a, n, c, m);
+      load_io<CV>(dy + ((size_t)(n * Ho + wy) * Wo + wx) * a.C + c, d);
+      chan_keep<CV>(a.drop, n, a.C, c, m);
 #pragma unroll
       for (int e = 0; e < CV; ++e) {
-        float best = fmaxf(__builtin_fmaf(zv[0][e], sc[e], sh[e]), 0.f);
-#pragma unroll
-        for (int q = 1; q < MAXW; ++q) {
-          if (!inb[q]) continue;
-          const float v = fmaxf(__builtin_fmaf(zv[q][e], sc[e], sh[e]), 0.f);
-          if (v > best) {
-            best = v;
-            arg[e] = q;
-          }
-        }
-        gv[e] = best > 0.f ? d[e] * m[e] : 0.f;
+        const float w[MAXW] = {zv[0][e], zv[1][e], zv[2][e], zv[3][e]};
+        const FirstMax r = route_first_max(w, sc[e], sh[e], P * P);
+        arg[e] = r.arg;
+        gv[e] = r.best > 0.f ? d[e] * m[e] : 0.f;
       }
     }
-    if (!APPLY) {
-      if (full) {
 #pragma unroll
-        for (int e = 0; e < CV; ++e) {
-          float zr = zv[0][e];
-#pragma unroll
-          for (int q = 1; q < MAXW; ++q) zr = arg[e] == q ? zv[q][e] : zr;
-          acc1[e] += gv[e];
-          acc2[e] += gv[e] * ((zr - mu[e]) * is[e]);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < MAXW; ++q) {
-        if (!inb[q]) continue;
-        float o[CV];
-#pragma unroll
-        for (int e = 0; e < CV; ++e) {
-          const float gq = arg[e] == q ? gv[e] : 0.f;
-          o[e] = training ? sc[e] * gq + ca[e] + cb[e] * zv[q][e] : sc[e] * gq;
-        }
-        const int y = wy * P + (q >> 1), x = wx * P + (q & 1);
-        V16<T>::store(dz + ((size_t)(n * a.H + y) * a.W + x) * a.C + c, o);
-      }
-    }
-  }
-  if (!APPLY) {
-    // every thread of a block keeps one channel group (256 % G == 0 and the
-    // grid stride is a multiple of G); reduce across the block, one atomic each
-#pragma unroll
-    for (int e = 0; e < CV; ++e) {
-      red[0][threadIdx.x][e] = acc1[e];
-      red[1][threadIdx.x][e] = acc2[e];
-    }
-    __syncthreads();
-    if (threadIdx.x < G) {
-      float t1[CV], t2[CV];
-#pragma unroll
-      for (int e = 0; e < CV; ++e) t1[e] = t2[e] = 0.f;
-      for (int k = threadIdx.x; k < 256; k += G)
-#pragma unroll
-        for (int e = 0; e < CV; ++e) {
-          t1[e] += red[0][k][e];
-          t2[e] += red[1][k][e];
-        }
-      // this workgroup's partial row (deterministic: no atomics)
-      float* slot = sums + 2 * a.C * (1 + blockIdx.x);
-      const int cc = threadIdx.x * CV;
+    for (int q = 0; q < MAXW; ++q) {
+      if (!inb[q]) continue;
+      float o[CV];
 #pragma unroll
       for (int e = 0; e < CV; ++e) {
-        slot[cc + e] = t1[e];
-        slot[a.C + cc + e] = t2[e];
+        const float gq = arg[e] == q ? gv[e] : 0.f;
+        // f32 z keeps the plain expression and with it the compiler's contraction, which is not
+        // bn_bwd_dz's: for two of the four channels it pairs sc*gq with cb*z in a packed multiply and
+        // adds both unfused.  The values stay bit for bit those of the code before bn_tail.h.
+        if constexpr (sizeof(T) == 2) o[e] = training ? bn_bwd_dz(sc[e], gq, ca[e], cb[e], zv[q][e]) : sc[e] * gq;
+        else o[e] = training ? sc[e] * gq + ca[e] + cb[e] * zv[q][e] : sc[e] * gq;
       }
+      const int y = wy * P + (q >> 1), x = wx * P + (q & 1);
+      store_chan<CV>(dz + ((size_t)(n * a.H + y) * a.W + x) * a.C + c, o);
     }
   }
 }
@@ -297,18 +198,12 @@ __global__ __launch_bounds__(256) void bnact_bwd_kernel(const T* __restrict__ z,
 // and of g * xhat over full pooling windows.  Software-pipelined: the next
 // window's z taps and dy are loaded (raw) before the current one is reduced,
 // so every thread keeps two windows of loads in flight.
-template <typename T>
-__device__ __forceinline__ float raw_elem(const u32x4& u, int e) {
-  if constexpr (sizeof(T) == 2) return __uint_as_float((e & 1) ? (u[e >> 1] & 0xffff0000u) : (u[e >> 1] << 16));
-  else return __uint_as_float(u[e]);
-}
-
 template <typename T, typename TD>
 __global__ __launch_bounds__(256) void bnact_sums_kernel(const T* __restrict__ z, const TD* __restrict__ dy,
                                                         BnArgs a_, float* __restrict__ sums) {
   BnArgs a = a_;
-  a.resolve();
-  constexpr int CV = V16<T>::N;
+  a.drop.resolve();
+  constexpr int CV = CV16<T>;
   constexpr int MAXW = 4;  // pool <= 2
   __shared__ float red[2][256][CV];
   const int G = a.C / CV;
@@ -316,19 +211,12 @@ __global__ __launch_bounds__(256) void bnact_sums_kernel(const T* __restrict__ z
   const int Ho = a.H / P, Wo = a.W / P;
   const int total = a.N * Ho * Wo * G;  // full windows only
   const int c = ((blockIdx.x * blockDim.x + threadIdx.x) % G) * CV;
-  float sc[CV], sh[CV], mu[CV], is[CV], acc1[CV], acc2[CV], ga_[CV], be_[CV];
-  load_cv<CV>(a.mean, c, mu);
-  load_cv<CV>(a.invstd, c, is);
-  load_cv<CV>(a.gamma, c, ga_);
-  load_cv<CV>(a.beta, c, be_);
+  float sc[CV], sh[CV], mu[CV], is[CV], acc1[CV], acc2[CV];
+  bn_consts<CV>(a, c, sc, sh, mu, is);
 #pragma unroll
-  for (int e = 0; e < CV; ++e) {
-    sc[e] = is[e] * ga_[e];
-    sh[e] = be_[e] - mu[e] * sc[e];
-    acc1[e] = acc2[e] = 0.f;
-  }
+  for (int e = 0; e < CV; ++e) acc1[e] = acc2[e] = 0.f;
   struct Item {
-    u32x4 zr[MAXW];
+    ChanVec<T, CV> zr[MAXW];
     float d[CV];
     int n;
   };
@@ -342,35 +230,20 @@ __global__ __launch_bounds__(256) void bnact_sums_kernel(const T* __restrict__ z
 #pragma unroll
     for (int q = 0; q < MAXW; ++q)
       if (q < P * P)
-        it.zr[q] = *(const u32x4*)(z + ((size_t)(it.n * a.H + wy * P + (q >> 1)) * a.W + wx * P + (q & 1)) * a.C + c);
-    const TD* dp = dy + ((size_t)(it.n * Ho + wy) * Wo + wx) * a.C + c;
-    if constexpr (sizeof(TD) == sizeof(T)) {
-      V16<TD>::load(dp, it.d);
-    } else {
-#pragma unroll
-      for (int e = 0; e < CV; ++e) it.d[e] = Elem<TD>::to_f(dp[e]);
-    }
+        it.zr[q].load(z + ((size_t)(it.n * a.H + wy * P + (q >> 1)) * a.W + wx * P + (q & 1)) * a.C + c);
+    load_io<CV>(dy + ((size_t)(it.n * Ho + wy) * Wo + wx) * a.C + c, it.d);
   };
   auto reduce = [&](const Item& it) {
     float m[CV];
-    drop_mask<CV>(a, it.n, c, m);
+    chan_keep<CV>(a.drop, it.n, a.C, c, m);
 #pragma unroll
     for (int e = 0; e < CV; ++e) {
-      float zs = raw_elem<T>(it.zr[0], e);
-      float best = fmaxf(__builtin_fmaf(zs, sc[e], sh[e]), 0.f);
-#pragma unroll
-      for (int q = 1; q < MAXW; ++q) {
-        if (q >= P * P) break;
-        const float zq = raw_elem<T>(it.zr[q], e);
-        const float v = fmaxf(__builtin_fmaf(zq, sc[e], sh[e]), 0.f);
-        if (v > best) {  // first maximum wins ties (torch's max-pool routing)
-          best = v;
-          zs = zq;
-        }
-      }
-      const float gv = best > 0.f ? it.d[e] * m[e] : 0.f;
+      // (converted one channel at a time: all four vectors as floats at once cost 17 VGPRs and a wave per SIMD)
+      const float w[MAXW] = {it.zr[0].at(e), it.zr[1].at(e), it.zr[2].at(e), it.zr[3].at(e)};
+      const FirstMax r = route_first_max(w, sc[e], sh[e], P * P);
+      const float gv = r.best > 0.f ? it.d[e] * m[e] : 0.f;
       acc1[e] += gv;
-      acc2[e] += gv * ((zs - mu[e]) * is[e]);
+      acc2[e] += gv * ((r.z - mu[e]) * is[e]);
     }
   };
   const int stride = gridDim.x * blockDim.x;
@@ -383,6 +256,8 @@ __global__ __launch_bounds__(256) void bnact_sums_kernel(const T* __restrict__ z
     reduce(cur);
     cur = nxt;
   }
+  // every thread of a block keeps one channel group (256 % G == 0 and the grid
+  // stride is a multiple of G): reduce across the block
 #pragma unroll
   for (int e = 0; e < CV; ++e) {
     red[0][threadIdx.x][e] = acc1[e];
@@ -431,12 +306,7 @@ static int make_args(BnArgs& a, int N, int H, int W, int C, int pool, const floa
   HVIT_CHECK((long)N * H * W * C < (1L << 31), "bn_act: tensor too large for 32-bit indexing");
   a.N = N; a.H = H; a.W = W; a.C = C; a.pool = pool;
   a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.beta = beta;
-  a.thr = dr ? drop_threshold(dr->p) : 0;
-  a.dscale = (dr && dr->p > 0.f) ? 1.f / (1.f - dr->p) : 1.f;
-  a.key = dr ? rng_key(dr->seed, dr->site) : 0u;
-  a.seedp = dr ? dr->seed_ptr : nullptr;
-  a.seed = dr ? dr->seed : 0ull;
-  a.site = dr ? dr->site : 0u;
+  a.drop = drop_key(dr);
   a.fG = FastDiv(C / cv);
   a.fWo = FastDiv(std::max(1, W / pool));
   a.fHo = FastDiv(std::max(1, H / pool));
@@ -461,14 +331,13 @@ extern "C" int hvit_bn_act_fwd(int dt, const void* z, int N, int H, int W, int C
   if (total <= 0) return HVIT_OK;
   hipStream_t st = (hipStream_t)stream;
   dim3 g(grid_for(total, BN_GRID_FWD));
-  if (dt == HVIT_BF16 && y_dt == HVIT_BF16)
-    hipLaunchKernelGGL((bnact_fwd_kernel<bf16_t, bf16_t>), g, dim3(256), 0, st, (const bf16_t*)z, (bf16_t*)y, a);
-  else if (dt == HVIT_BF16)
-    hipLaunchKernelGGL((bnact_fwd_kernel<bf16_t, float>), g, dim3(256), 0, st, (const bf16_t*)z, (float*)y, a);
-  else if (y_dt == HVIT_F32)
-    hipLaunchKernelGGL((bnact_fwd_kernel<float, float>), g, dim3(256), 0, st, (const float*)z, (float*)y, a);
-  else
-    hipLaunchKernelGGL((bnact_fwd_kernel<float, bf16_t>), g, dim3(256), 0, st, (const float*)z, (bf16_t*)y, a);
+  with_elem(dt, [&](auto t) {
+    with_elem(y_dt, [&](auto to) {
+      using T = decltype(t);
+      using TO = decltype(to);
+      hipLaunchKernelGGL((bnact_fwd_kernel<T, TO>), g, dim3(256), 0, st, (const T*)z, (TO*)y, a);
+    });
+  });
   HVIT_LAUNCH_CHECK();
   return HVIT_OK;
 }
@@ -491,7 +360,7 @@ static int bnact_bwd_t(const void* z, const void* dy, const BnArgs& a, float* su
     // sums[0 .. 2C) = the partial rows summed in row order (0 rows: zeros)
     if (int rc = hvit_reduce_rows(sums + 2 * a.C, HVIT_F32, gs, 2 * a.C, 2 * a.C, 0, sums, st)) return rc;
   }
-  hipLaunchKernelGGL((bnact_bwd_kernel<T, TD, true>), ga, dim3(256), 0, st, (const T*)z, (const TD*)dy, a, sums,
+  hipLaunchKernelGGL((bnact_bwd_kernel<T, TD>), ga, dim3(256), 0, st, (const T*)z, (const TD*)dy, a, sums,
                      training, (T*)dz);
   HVIT_LAUNCH_CHECK();
   return HVIT_OK;
@@ -511,9 +380,9 @@ extern "C" int hvit_bn_act_bwd(int dt, const void* z, int N, int H, int W, int C
   if (int rc = make_args(a, N, H, W, C, pool, mean, invstd, gamma, beta, dropout2d, cv)) return rc;
   hipStream_t st = (hipStream_t)stream;
   (void)flags;  // (the partial rows are plain stores: no zeroed accumulator needed)
-  if (dt == HVIT_BF16)
-    return dy_dt == HVIT_BF16 ? bnact_bwd_t<bf16_t, bf16_t>(z, dy, a, sums, training, dz, st)
-                              : bnact_bwd_t<bf16_t, float>(z, dy, a, sums, training, dz, st);
-  return dy_dt == HVIT_BF16 ? bnact_bwd_t<float, bf16_t>(z, dy, a, sums, training, dz, st)
-                            : bnact_bwd_t<float, float>(z, dy, a, sums, training, dz, st);
+  int rc = HVIT_OK;
+  with_elem(dt, [&](auto t) {
+    with_elem(dy_dt, [&](auto td) { rc = bnact_bwd_t<decltype(t), decltype(td)>(z, dy, a, sums, training, dz, st); });
+  });
+  return rc;
 }

@@ -22,9 +22,13 @@
 
 #include <type_traits>
 
+#include "bn_tail.h"
+#include "chan_vec.h"
 #include "common.h"
 
 namespace hvit_c1 {
+
+using namespace hvit;  // bn_tail.h
 
 // the backward sums' partial rows: one [2C] row per sums workgroup, written
 // into the weight-gradient workspace (which the backward kernel overwrites only
@@ -40,15 +44,7 @@ struct Args {
   const float* invstd;
   const float* gamma;
   const float* beta;
-  uint32_t thr;
-  float dscale;
-  uint32_t key;
-  const unsigned long long* seedp;
-  unsigned long long seed;
-  uint32_t site;
-  __device__ __forceinline__ void resolve() {
-    if (seedp && thr) key = rng_key(seed ^ *seedp, site);
-  }
+  DropKey drop;
 };
 
 template <typename T>
@@ -121,88 +117,23 @@ __device__ __forceinline__ void load_w(const Args& a, int c, float (&wr)[9][CV])
     for (int e = 0; e < CV; ++e) wr[t][e] = ldv<T>(a.w, (c + e) * 9 + t);
 }
 
-template <int CV>
-__device__ __forceinline__ void loadc(const float* p, int c, float* o) {
-#pragma unroll
-  for (int e = 0; e < CV; ++e) o[e] = p[c + e];
-}
-
 // relu(bn(z)) = max(z*sc + sh, 0); xhat = (z - mu)*is
 template <int CV>
 __device__ __forceinline__ void bn_consts(const Args& a, int c, float* sc, float* sh, float* mu, float* is) {
   float ga[CV], be[CV];
-  loadc<CV>(a.mean, c, mu);
-  loadc<CV>(a.invstd, c, is);
-  loadc<CV>(a.gamma, c, ga);
-  loadc<CV>(a.beta, c, be);
+  load_chan<CV>(a.mean + c, mu);
+  load_chan<CV>(a.invstd + c, is);
+  load_chan<CV>(a.gamma + c, ga);
+  load_chan<CV>(a.beta + c, be);
 #pragma unroll
-  for (int e = 0; e < CV; ++e) {
-    sc[e] = is[e] * ga[e];
-    sh[e] = be[e] - mu[e] * sc[e];
-  }
-}
-
-// Dropout2d multipliers of channels c .. c+CV-1 of sample n (bnact.hip drop_mask)
-template <int CV>
-__device__ __forceinline__ void drop_cv(const Args& a, int n, int c, float* m) {
-#pragma unroll
-  for (int e = 0; e < CV; ++e) m[e] = 1.f;
-  if (!a.thr) return;
-  const uint64_t i0 = (uint64_t)n * a.C + c;
-#pragma unroll
-  for (int e4 = 0; e4 < CV; e4 += 4) {
-    const f32x4 k = keep4_at(a.key, i0 + e4, a.thr, a.dscale);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) m[e4 + e] = k[e];
-  }
-}
-
-template <typename TO, int CV>
-__device__ __forceinline__ void store_cv(TO* p, const float* v) {
-  if constexpr (sizeof(TO) == 2) {
-    uint32_t u[CV / 2];
-#pragma unroll
-    for (int i = 0; i < CV / 2; ++i) u[i] = f2bf2(v[2 * i], v[2 * i + 1]);
-    if constexpr (CV == 8) *(u32x4*)p = (u32x4){u[0], u[1], u[2], u[3]};
-    else *(uint2*)p = make_uint2(u[0], u[1]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < CV; i += 4) *(f32x4*)(p + i) = (f32x4){v[i], v[i + 1], v[i + 2], v[i + 3]};
-  }
-}
-template <typename TD, int CV>
-__device__ __forceinline__ void load_cv(const TD* p, float* v) {
-  if constexpr (sizeof(TD) == 2) {
-    uint32_t u[CV / 2];
-    if constexpr (CV == 8) {
-      const u32x4 q = *(const u32x4*)p;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) u[i] = q[i];
-    } else {
-      const uint2 q = *(const uint2*)p;
-      u[0] = q.x;
-      u[1] = q.y;
-    }
-#pragma unroll
-    for (int i = 0; i < CV / 2; ++i) {
-      v[2 * i] = __uint_as_float(u[i] << 16);
-      v[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < CV; i += 4) {
-      const f32x4 q = *(const f32x4*)(p + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[i + j] = q[j];
-    }
-  }
+  for (int e = 0; e < CV; ++e) bn_scale_shift(mu[e], is[e], ga[e], be[e], sc[e], sh[e]);
 }
 
 // forward apply: y[n, oy, ox, c..] = Dropout2d(max over the window of relu(bn(z)))
 template <typename T, typename TO, int P, int CV>
 __global__ __launch_bounds__(THREADS) void c1_apply_kernel(Args a_, TO* __restrict__ y) {
   Args a = a_;
-  a.resolve();
+  a.drop.resolve();
   extern __shared__ __attribute__((aligned(16))) float xs[];
   const int Ho = a.H / P, Wo = a.W / P;
   const int chunks = (Ho + a.RB - 1) / a.RB;
@@ -213,7 +144,7 @@ __global__ __launch_bounds__(THREADS) void c1_apply_kernel(Args a_, TO* __restri
   float wr[9][CV], sc[CV], sh[CV], mu[CV], is[CV], m[CV];
   load_w<T, CV>(a, c, wr);
   bn_consts<CV>(a, c, sc, sh, mu, is);
-  drop_cv<CV>(a, n, c, m);
+  chan_keep<CV>(a.drop, n, a.C, c, m);
   const int rows = min(a.RB, Ho - oy0);
   for (int it = threadIdx.x / CC; it < rows * Wo; it += lanes) {
     int r, ox;
@@ -232,7 +163,7 @@ __global__ __launch_bounds__(THREADS) void c1_apply_kernel(Args a_, TO* __restri
     }
 #pragma unroll
     for (int e = 0; e < CV; ++e) best[e] *= m[e];
-    store_cv<TO, CV>(y + (((long)n * Ho + oy0 + r) * Wo + ox) * a.C + c, best);
+    store_chan<CV>(y + (((long)n * Ho + oy0 + r) * Wo + ox) * a.C + c, best);
   }
 }
 
@@ -244,20 +175,13 @@ __device__ __forceinline__ void route(const float (&zq)[P * P][CV], const float*
                                       const float* m, int* arg, float* g, float* zs) {
 #pragma unroll
   for (int e = 0; e < CV; ++e) {
-    float best = fmaxf(__builtin_fmaf(zq[0][e], sc[e], sh[e]), 0.f);
-    float z = zq[0][e];
-    int ai = 0;
+    float w[P * P];
 #pragma unroll
-    for (int q = 1; q < P * P; ++q) {
-      const float v = fmaxf(__builtin_fmaf(zq[q][e], sc[e], sh[e]), 0.f);
-      const bool gt = v > best;
-      best = gt ? v : best;
-      z = gt ? zq[q][e] : z;
-      ai = gt ? q : ai;
-    }
-    arg[e] = ai;
-    g[e] = best > 0.f ? d[e] * m[e] : 0.f;
-    zs[e] = z;
+    for (int q = 0; q < P * P; ++q) w[q] = zq[q][e];
+    const FirstMax r = route_first_max(w, sc[e], sh[e]);
+    arg[e] = r.arg;
+    g[e] = r.best > 0.f ? d[e] * m[e] : 0.f;
+    zs[e] = r.z;
   }
 }
 
@@ -266,7 +190,7 @@ __device__ __forceinline__ void route(const float (&zq)[P * P][CV], const float*
 template <typename T, typename TD, int P, int CV>
 __global__ __launch_bounds__(THREADS) void c1_sums_kernel(Args a_, const TD* __restrict__ dy, float* __restrict__ part) {
   Args a = a_;
-  a.resolve();
+  a.drop.resolve();
   extern __shared__ __attribute__((aligned(16))) float xs[];
   const int Ho = a.H / P, Wo = a.W / P;
   const int chunks = (Ho + a.RB - 1) / a.RB;
@@ -279,7 +203,7 @@ __global__ __launch_bounds__(THREADS) void c1_sums_kernel(Args a_, const TD* __r
   float wr[9][CV], sc[CV], sh[CV], mu[CV], is[CV], m[CV], acc1[CV], acc2[CV];
   load_w<T, CV>(a, c, wr);
   bn_consts<CV>(a, c, sc, sh, mu, is);
-  drop_cv<CV>(a, n, c, m);
+  chan_keep<CV>(a.drop, n, a.C, c, m);
 #pragma unroll
   for (int e = 0; e < CV; ++e) acc1[e] = acc2[e] = 0.f;
   const int rows = min(a.RB, Ho - oy0);
@@ -287,7 +211,7 @@ __global__ __launch_bounds__(THREADS) void c1_sums_kernel(Args a_, const TD* __r
     int r, ox;
     win_rc(it, Wo, r, ox);
     float d[CV];
-    load_cv<TD, CV>(dy + (((long)n * Ho + oy0 + r) * Wo + ox) * a.C + c, d);
+    load_chan<CV>(dy + (((long)n * Ho + oy0 + r) * Wo + ox) * a.C + c, d);
     float pt[P + 2][P + 2];
     load_patch<P>(xs, pitch, r, ox, pt);
     float zq[P * P][CV];
@@ -329,7 +253,7 @@ __global__ __launch_bounds__(THREADS) void c1_bwd_kernel(Args a_, const TD* __re
                                                          const float* __restrict__ sums, int training,
                                                          float* __restrict__ part) {
   Args a = a_;
-  a.resolve();
+  a.drop.resolve();
   extern __shared__ __attribute__((aligned(16))) float xs[];
   constexpr int lanes = THREADS / CC;
   const int Ho = a.H / P, Wo = a.W / P;
@@ -347,17 +271,12 @@ __global__ __launch_bounds__(THREADS) void c1_bwd_kernel(Args a_, const TD* __re
   {
     float mu[CV], is[CV], s1v[CV], s2v[CV];
     bn_consts<CV>(a, c, sc, sh, mu, is);
-    loadc<CV>(sums, c, s1v);
-    loadc<CV>(sums + a.C, c, s2v);
-    // dz = sc*(g - s1 - xhat*s2) = sc*g + ca + cb*z  (bnact.hip's apply pass)
+    load_chan<CV>(sums + c, s1v);
+    load_chan<CV>(sums + a.C + c, s2v);
 #pragma unroll
-    for (int e = 0; e < CV; ++e) {
-      const float s1 = training ? s1v[e] * invM : 0.f, s2 = training ? s2v[e] * invM : 0.f;
-      cb[e] = -sc[e] * s2 * is[e];
-      ca[e] = -sc[e] * s1 - cb[e] * mu[e];
-    }
+    for (int e = 0; e < CV; ++e) bn_bwd_coeffs(sc[e], mu[e], is[e], s1v[e], s2v[e], invM, training, ca[e], cb[e]);
   }
-  drop_cv<CV>(a, n, c, m);
+  chan_keep<CV>(a.drop, n, a.C, c, m);
   float acc[9][CV];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
@@ -372,7 +291,7 @@ __global__ __launch_bounds__(THREADS) void c1_bwd_kernel(Args a_, const TD* __re
     float d[CV];
 #pragma unroll
     for (int e = 0; e < CV; ++e) d[e] = 0.f;
-    if (full) load_cv<TD, CV>(dy + (((long)n * Ho + oy) * Wo + ox) * a.C + c, d);
+    if (full) load_chan<CV>(dy + (((long)n * Ho + oy) * Wo + ox) * a.C + c, d);
     float pt[P + 2][P + 2];
     load_patch<P>(xs, pitch, r, ox, pt);
     float zq[P * P][CV];
@@ -389,7 +308,7 @@ __global__ __launch_bounds__(THREADS) void c1_bwd_kernel(Args a_, const TD* __re
 #pragma unroll
       for (int e = 0; e < CV; ++e) {
         const float gq = arg[e] == q ? g[e] : 0.f;
-        const float dz = inb * (training ? sc[e] * gq + ca[e] + cb[e] * zq[q][e] : sc[e] * gq);
+        const float dz = inb * (training ? bn_bwd_dz(sc[e], gq, ca[e], cb[e], zq[q][e]) : sc[e] * gq);
 #pragma unroll
         for (int t = 0; t < 9; ++t) acc[t][e] += dz * pt[qy + t / 3][qx + t % 3];
       }
@@ -474,94 +393,15 @@ struct ChanConsts {
       const int c = c0 + cb;
       mu[cb] = a.mean[c];
       is[cb] = a.invstd[c];
-      sc[cb] = is[cb] * a.gamma[c];
-      sh[cb] = a.beta[c] - mu[cb] * sc[cb];
-      m[cb] = a.thr ? (rng_u16k(a.key, (uint64_t)n * a.C + c) >= a.thr ? a.dscale : 0.f) : 1.f;
+      bn_scale_shift(mu[cb], is[cb], a.gamma[c], a.beta[c], sc[cb], sh[cb]);
+      chan_keep<1>(a.drop, n, a.C, c, &m[cb]);
     }
   }
 };
 
-template <typename TD, int NCB>
-__device__ __forceinline__ void load_ncb(const TD* p, float* v) {
-  if constexpr (sizeof(TD) == 2) {
-    if constexpr (NCB == 4) {
-      const uint2 q = *(const uint2*)p;
-      v[0] = __uint_as_float(q.x << 16);
-      v[1] = __uint_as_float(q.x & 0xffff0000u);
-      v[2] = __uint_as_float(q.y << 16);
-      v[3] = __uint_as_float(q.y & 0xffff0000u);
-    } else if constexpr (NCB == 2) {
-      const uint32_t q = *(const uint32_t*)p;
-      v[0] = __uint_as_float(q << 16);
-      v[1] = __uint_as_float(q & 0xffff0000u);
-    } else {
-      v[0] = bf2f(p[0]);
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < NCB; ++e) v[e] = p[e];
-  }
-}
-// the same NCB channels as raw bits, converted at their use: the load of the
-// next window group is issued before the current one's arithmetic (the dy
-// stream was latency-bound: one dependent HBM round trip per group)
-template <typename TD, int NCB>
-struct RawNcb {
-  float v[NCB];
-  __device__ __forceinline__ void load(const TD* p) {
-#pragma unroll
-    for (int e = 0; e < NCB; ++e) v[e] = p[e];
-  }
-  __device__ __forceinline__ void get(float* o) const {
-#pragma unroll
-    for (int e = 0; e < NCB; ++e) o[e] = v[e];
-  }
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int e = 0; e < NCB; ++e) v[e] = 0.f;
-  }
-};
-template <>
-struct RawNcb<bf16_t, 4> {
-  uint2 q;
-  __device__ __forceinline__ void load(const bf16_t* p) { q = *(const uint2*)p; }
-  __device__ __forceinline__ void get(float* o) const {
-    o[0] = __uint_as_float(q.x << 16);
-    o[1] = __uint_as_float(q.x & 0xffff0000u);
-    o[2] = __uint_as_float(q.y << 16);
-    o[3] = __uint_as_float(q.y & 0xffff0000u);
-  }
-  __device__ __forceinline__ void zero() { q = make_uint2(0u, 0u); }
-};
-template <>
-struct RawNcb<bf16_t, 2> {
-  uint32_t q;
-  __device__ __forceinline__ void load(const bf16_t* p) { q = *(const uint32_t*)p; }
-  __device__ __forceinline__ void get(float* o) const {
-    o[0] = __uint_as_float(q << 16);
-    o[1] = __uint_as_float(q & 0xffff0000u);
-  }
-  __device__ __forceinline__ void zero() { q = 0u; }
-};
-template <>
-struct RawNcb<bf16_t, 1> {
-  bf16_t q;
-  __device__ __forceinline__ void load(const bf16_t* p) { q = *p; }
-  __device__ __forceinline__ void get(float* o) const { o[0] = bf2f(q); }
-  __device__ __forceinline__ void zero() { q = 0; }
-};
-
-template <typename TO, int NCB>
-__device__ __forceinline__ void store_ncb(TO* p, const float* v) {
-  if constexpr (sizeof(TO) == 2) {
-    if constexpr (NCB == 4) *(uint2*)p = make_uint2(f2bf2(v[0], v[1]), f2bf2(v[2], v[3]));
-    else if constexpr (NCB == 2) *(uint32_t*)p = f2bf2(v[0], v[1]);
-    else p[0] = f2bf(v[0]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < NCB; ++e) p[e] = v[e];
-  }
-}
+// dy of the c1m kernels stays raw (ChanVec) until used: the load of the next
+// window group is issued before the current one's arithmetic (the dy stream
+// was latency-bound: one dependent HBM round trip per group)
 
 // z of the 16 rows of window group g (windows 4g .. 4g+3 of the block, row-major
 // over rows x ww windows per row), one accumulator per channel block.  Windows
@@ -582,26 +422,10 @@ __device__ __forceinline__ void group_z(const float* xs, int pitch, int g, int n
   for (int cb = 0; cb < NCB; ++cb) z[cb] = mfma16(af, bw[cb], (f32x4){0.f, 0.f, 0.f, 0.f});
 }
 
-// first-maximum routing of one window (4 positions in registers): arg, relu'd
-// maximum, z at the maximum
-__device__ __forceinline__ void route4(const f32x4& z, float sc, float sh, int& arg, float& best, float& zs) {
-  best = fmaxf(__builtin_fmaf(z[0], sc, sh), 0.f);
-  zs = z[0];
-  arg = 0;
-#pragma unroll
-  for (int q = 1; q < 4; ++q) {
-    const float v = fmaxf(__builtin_fmaf(z[q], sc, sh), 0.f);
-    const bool gt = v > best;
-    best = gt ? v : best;
-    zs = gt ? z[q] : zs;
-    arg = gt ? q : arg;
-  }
-}
-
 template <typename TO, int NCB>
 __global__ __launch_bounds__(THREADS) void c1m_apply_kernel(Args a_, TO* __restrict__ y) {
   Args a = a_;
-  a.resolve();
+  a.drop.resolve();
   extern __shared__ __attribute__((aligned(16))) float xs[];
   const int Ho = a.H / 2, Wo = a.W / 2;
   const int chunks = (Ho + a.RB - 1) / a.RB;
@@ -630,7 +454,7 @@ __global__ __launch_bounds__(THREADS) void c1m_apply_kernel(Args a_, TO* __restr
         for (int q = 0; q < 4; ++q) best = fmaxf(best, __builtin_fmaf(z[cb][q], k.sc[cb], k.sh[cb]));
         o[cb] = best * k.m[cb];
       }
-      store_ncb<TO, NCB>(y + (((long)n * Ho + oy0 + r) * Wo + ox) * a.C + c0, o);
+      store_chan<NCB>(y + (((long)n * Ho + oy0 + r) * Wo + ox) * a.C + c0, o);
     }
   }
 }
@@ -639,7 +463,7 @@ template <typename TD, int NCB>
 __global__ __launch_bounds__(THREADS) void c1m_sums_kernel(Args a_, const TD* __restrict__ dy,
                                                            float* __restrict__ part) {
   Args a = a_;
-  a.resolve();
+  a.drop.resolve();
   extern __shared__ __attribute__((aligned(16))) float xs[];
   const int Ho = a.H / 2, Wo = a.W / 2;
   const int chunks = (Ho + a.RB - 1) / a.RB;
@@ -659,7 +483,7 @@ __global__ __launch_bounds__(THREADS) void c1m_sums_kernel(Args a_, const TD* __
   for (int cb = 0; cb < NCB; ++cb) s1[cb] = s2[cb] = 0.f;
   const int nwin = min(a.RB, Ho - oy0) * Wo;
   // dy of group g for this lane (window 4g + (l >> 4)), one group ahead
-  auto issue = [&](int g, RawNcb<TD, NCB>& raw) {
+  auto issue = [&](int g, ChanVec<TD, NCB>& raw) {
     const int it = 4 * g + (l >> 4);
     if (4 * g < nwin && it < nwin) {
       int r, ox;
@@ -669,10 +493,10 @@ __global__ __launch_bounds__(THREADS) void c1m_sums_kernel(Args a_, const TD* __
       raw.zero();
     }
   };
-  RawNcb<TD, NCB> nxt;
+  ChanVec<TD, NCB> nxt;
   issue(wv, nxt);
   for (int g = wv; 4 * g < nwin; g += THREADS / 64) {
-    const RawNcb<TD, NCB> cur = nxt;
+    const ChanVec<TD, NCB> cur = nxt;
     issue(g + THREADS / 64, nxt);
     f32x4 z[NCB];
     group_z<NCB>(xs, pitch, g, nwin, Wo, l, bw, z);
@@ -682,12 +506,11 @@ __global__ __launch_bounds__(THREADS) void c1m_sums_kernel(Args a_, const TD* __
       cur.get(d);
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
-        int arg;
-        float best, zs;
-        route4(z[cb], k.sc[cb], k.sh[cb], arg, best, zs);
-        const float gv = best > 0.f ? d[cb] * k.m[cb] : 0.f;
+        const float zw[4] = {z[cb][0], z[cb][1], z[cb][2], z[cb][3]};
+        const FirstMax r = route_first_max(zw, k.sc[cb], k.sh[cb]);
+        const float gv = r.best > 0.f ? d[cb] * k.m[cb] : 0.f;
         s1[cb] += gv;
-        s2[cb] += gv * ((zs - k.mu[cb]) * k.is[cb]);
+        s2[cb] += gv * ((r.z - k.mu[cb]) * k.is[cb]);
       }
     }
   }
@@ -716,7 +539,7 @@ __global__ __launch_bounds__(THREADS) void c1m_bwd_kernel(Args a_, const TD* __r
                                                           const float* __restrict__ sums, int training,
                                                           float* __restrict__ part) {
   Args a = a_;
-  a.resolve();
+  a.drop.resolve();
   extern __shared__ __attribute__((aligned(16))) float xs[];
   const int Ho = a.H / 2, Wo = a.W / 2;
   const int Hw = (a.H + 1) / 2, Ww = (a.W + 1) / 2;
@@ -736,6 +559,9 @@ __global__ __launch_bounds__(THREADS) void c1m_bwd_kernel(Args a_, const TD* __r
   float ca[NCB], cbz[NCB];
   const float invM = 1.f / (float)((long)a.N * a.H * a.W);
 #pragma unroll
+  // (bn_bwd_coeffs' expressions, kept here: through the shared function, which takes the sums as values and
+  // so loads them in eval mode too, the NCB = 4 FULL kernel took 172 VGPRs instead of 168 -- two waves per SIMD
+  // instead of three -- and c1block_bwd measured 0.150-0.154 ms per step against 0.149-0.150)
   for (int cb = 0; cb < NCB; ++cb) {
     const float s1 = training ? sums[c0 + cb] * invM : 0.f, s2 = training ? sums[a.C + c0 + cb] * invM : 0.f;
     cbz[cb] = -k.sc[cb] * s2 * k.is[cb];
@@ -751,7 +577,7 @@ __global__ __launch_bounds__(THREADS) void c1m_bwd_kernel(Args a_, const TD* __r
   const int nwin = min(a.RB, Hw - oy0) * Ww;
   // dy of group g for this lane (zero outside the full windows), issued one
   // iteration (two groups) ahead
-  auto issue = [&](int g, RawNcb<TD, NCB>& raw) {
+  auto issue = [&](int g, ChanVec<TD, NCB>& raw) {
     const int it = 4 * g + (l >> 4);
     // (prefetches run past the block's last group: the window range test stays)
     const int itc = min(it, nwin - 1);
@@ -761,13 +587,13 @@ __global__ __launch_bounds__(THREADS) void c1m_bwd_kernel(Args a_, const TD* __r
     if (it < nwin && (FULL || (oy < Ho && ox < Wo))) raw.load(dy + (((long)n * Ho + oy) * Wo + ox) * a.C + c0);
     else raw.zero();
   };
-  RawNcb<TD, NCB> nxt[2];
+  ChanVec<TD, NCB> nxt[2];
   issue(2 * wv, nxt[0]);
   issue(2 * wv + 1, nxt[1]);
   for (int g0 = 2 * wv; 4 * g0 < nwin; g0 += 2 * (THREADS / 64)) {
     u32x4 bhi[NCB], blo[NCB];
     float xa[8];
-    const RawNcb<TD, NCB> cur[2] = {nxt[0], nxt[1]};
+    const ChanVec<TD, NCB> cur[2] = {nxt[0], nxt[1]};
     issue(g0 + 2 * (THREADS / 64), nxt[0]);
     issue(g0 + 2 * (THREADS / 64) + 1, nxt[1]);
 #pragma unroll
@@ -790,15 +616,14 @@ __global__ __launch_bounds__(THREADS) void c1m_bwd_kernel(Args a_, const TD* __r
         inb[q] = (FULL || (valid && oy * 2 + (q >> 1) < a.H && ox * 2 + (q & 1) < a.W)) ? 1.f : 0.f;
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
-        int arg;
-        float best, zs;
-        route4(z[cb], k.sc[cb], k.sh[cb], arg, best, zs);
-        const float gv = best > 0.f ? d[cb] * k.m[cb] : 0.f;
+        const float zw[4] = {z[cb][0], z[cb][1], z[cb][2], z[cb][3]};
+        const FirstMax r = route_first_max(zw, k.sc[cb], k.sh[cb]);
+        const float gv = r.best > 0.f ? d[cb] * k.m[cb] : 0.f;
         float dz[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const float gq = arg == q ? gv : 0.f;
-          const float v = fmaf(cbz[cb], z[cb][q], fmaf(k.sc[cb], gq, ca[cb]));  // ca = cbz = 0 in eval
+          const float gq = r.arg == q ? gv : 0.f;
+          const float v = bn_bwd_dz(k.sc[cb], gq, ca[cb], cbz[cb], z[cb][q]);  // ca = cbz = 0 in eval
           dz[q] = FULL ? v : inb[q] * v;
         }
         float lo[4];
@@ -955,6 +780,8 @@ int make_args(Args& a, int dt, const hvit_conv_geom_t* g, const void* w, const f
              "c1block: Cout=%d must be a power of two in [8, 256]", g->Cout);
   HVIT_CHECK(pool == 1 || pool == 2, "c1block: pool must be 1 or 2");
   HVIT_CHECK(dt == HVIT_BF16 || dt == HVIT_F32, "c1block: bad dtype");
+  HVIT_CHECK(aligned16(mean) && aligned16(invstd) && aligned16(gamma) && aligned16(beta),
+             "c1block: statistics / affine vectors must be 16-byte aligned");
   a.x = g->src1;
   a.w = w;
   a.N = g->N;
@@ -967,12 +794,7 @@ int make_args(Args& a, int dt, const hvit_conv_geom_t* g, const void* w, const f
   a.invstd = invstd;
   a.gamma = gamma;
   a.beta = beta;
-  a.thr = dr ? drop_threshold(dr->p) : 0;
-  a.dscale = (dr && dr->p > 0.f) ? 1.f / (1.f - dr->p) : 1.f;
-  a.key = dr ? rng_key(dr->seed, dr->site) : 0u;
-  a.seedp = dr ? dr->seed_ptr : nullptr;
-  a.seed = dr ? dr->seed : 0ull;
-  a.site = dr ? dr->site : 0u;
+  a.drop = drop_key(dr);
   return HVIT_OK;
 }
 
@@ -1040,10 +862,10 @@ extern "C" int hvit_c1block_fwd(int dt, const hvit_conv_geom_t* g, const void* w
     const size_t lds = sizeof(float) * (a.RB * 2 + 2) * (a.W + 4);
     with_ncb(a.C, [&](auto nc) {
       constexpr int NCB = decltype(nc)::value;
-      if (y_dt == HVIT_BF16)
-        hipLaunchKernelGGL((c1m_apply_kernel<bf16_t, NCB>), dim3(blocks), dim3(THREADS), lds, st, a, (bf16_t*)y);
-      else
-        hipLaunchKernelGGL((c1m_apply_kernel<float, NCB>), dim3(blocks), dim3(THREADS), lds, st, a, (float*)y);
+      with_elem(y_dt, [&](auto to) {
+        using TO = decltype(to);
+        hipLaunchKernelGGL((c1m_apply_kernel<TO, NCB>), dim3(blocks), dim3(THREADS), lds, st, a, (TO*)y);
+      });
     });
     HVIT_LAUNCH_CHECK();
     return HVIT_OK;
@@ -1051,16 +873,13 @@ extern "C" int hvit_c1block_fwd(int dt, const hvit_conv_geom_t* g, const void* w
   const size_t lds = sizeof(float) * (a.RB * pool + 2) * (a.W + 2);
   with_pool(pool, [&](auto pc) {
     constexpr int P = decltype(pc)::value;
-    if (dt == HVIT_BF16 && y_dt == HVIT_BF16)
-      hipLaunchKernelGGL((c1_apply_kernel<bf16_t, bf16_t, P, 8>), dim3(blocks), dim3(THREADS), lds, st, a,
-                         (bf16_t*)y);
-    else if (dt == HVIT_BF16)
-      hipLaunchKernelGGL((c1_apply_kernel<bf16_t, float, P, 8>), dim3(blocks), dim3(THREADS), lds, st, a, (float*)y);
-    else if (y_dt == HVIT_F32)
-      hipLaunchKernelGGL((c1_apply_kernel<float, float, P, 8>), dim3(blocks), dim3(THREADS), lds, st, a, (float*)y);
-    else
-      hipLaunchKernelGGL((c1_apply_kernel<float, bf16_t, P, 8>), dim3(blocks), dim3(THREADS), lds, st, a,
-                         (bf16_t*)y);
+    with_elem(dt, [&](auto t) {
+      with_elem(y_dt, [&](auto to) {
+        using T = decltype(t);
+        using TO = decltype(to);
+        hipLaunchKernelGGL((c1_apply_kernel<T, TO, P, 8>), dim3(blocks), dim3(THREADS), lds, st, a, (TO*)y);
+      });
+    });
   });
   HVIT_LAUNCH_CHECK();
   return HVIT_OK;
@@ -1085,7 +904,7 @@ extern "C" int hvit_c1block_bwd(int dt, const hvit_conv_geom_t* g, const void* w
   if (int rc = make_args(a, dt, g, w_packed, mean, invstd, gamma, beta, dropout2d, pool)) return rc;
   HVIT_CHECK(dy && sums && dw_packed && ws, "hvit_c1block_bwd: null pointer");
   HVIT_CHECK(dy_dt == HVIT_BF16 || dy_dt == HVIT_F32, "hvit_c1block_bwd: bad dy dtype");
-  HVIT_CHECK(aligned16(dy), "hvit_c1block_bwd: dy alignment");
+  HVIT_CHECK(aligned16(dy) && aligned16(sums), "hvit_c1block_bwd: dy / sums alignment");
   HVIT_CHECK(ws_elems >= hvit_c1block_bwd_ws(g, pool), "hvit_c1block_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int C = a.C;
@@ -1105,28 +924,22 @@ extern "C" int hvit_c1block_bwd(int dt, const hvit_conv_geom_t* g, const void* w
     if (mf) {
       with_ncb(C, [&](auto nc) {
         constexpr int NCB = decltype(nc)::value;
-        if (dy_dt == HVIT_BF16)
-          hipLaunchKernelGGL((c1m_sums_kernel<bf16_t, NCB>), dim3(blocks), dim3(THREADS), lds, st, a,
-                             (const bf16_t*)dy, ws);
-        else
-          hipLaunchKernelGGL((c1m_sums_kernel<float, NCB>), dim3(blocks), dim3(THREADS), lds, st, a,
-                             (const float*)dy, ws);
+        with_elem(dy_dt, [&](auto td) {
+          using TD = decltype(td);
+          hipLaunchKernelGGL((c1m_sums_kernel<TD, NCB>), dim3(blocks), dim3(THREADS), lds, st, a, (const TD*)dy, ws);
+        });
       });
     } else {
       with_pool(pool, [&](auto pc) {
         constexpr int P = decltype(pc)::value;
-        if (dt == HVIT_BF16 && dy_dt == HVIT_BF16)
-          hipLaunchKernelGGL((c1_sums_kernel<bf16_t, bf16_t, P, CV>), dim3(blocks), dim3(THREADS), lds, st, a,
-                             (const bf16_t*)dy, ws);
-        else if (dt == HVIT_BF16)
-          hipLaunchKernelGGL((c1_sums_kernel<bf16_t, float, P, CV>), dim3(blocks), dim3(THREADS), lds, st, a,
-                             (const float*)dy, ws);
-        else if (dy_dt == HVIT_BF16)
-          hipLaunchKernelGGL((c1_sums_kernel<float, bf16_t, P, CV>), dim3(blocks), dim3(THREADS), lds, st, a,
-                             (const bf16_t*)dy, ws);
-        else
-          hipLaunchKernelGGL((c1_sums_kernel<float, float, P, CV>), dim3(blocks), dim3(THREADS), lds, st, a,
-                             (const float*)dy, ws);
+        with_elem(dt, [&](auto t) {
+          with_elem(dy_dt, [&](auto td) {
+            using T = decltype(t);
+            using TD = decltype(td);
+            hipLaunchKernelGGL((c1_sums_kernel<T, TD, P, CV>), dim3(blocks), dim3(THREADS), lds, st, a,
+                               (const TD*)dy, ws);
+          });
+        });
       });
     }
     HVIT_LAUNCH_CHECK();
@@ -1144,15 +957,13 @@ extern "C" int hvit_c1block_bwd(int dt, const hvit_conv_geom_t* g, const void* w
       constexpr int NCB = decltype(nc)::value;
       const int Ww = (a.W + pool - 1) / pool;
       const bool full = pool == 2 && a.H % 2 == 0 && a.W % 2 == 0 && Hw % a.RB == 0 && (a.RB * Ww) % 8 == 0;
-      if (dy_dt == HVIT_BF16 && full)
-        hipLaunchKernelGGL((c1m_bwd_kernel<bf16_t, NCB, true>), dim3(blocks), dim3(THREADS), lds, st, a,
-                           (const bf16_t*)dy, sums, training, ws);
-      else if (dy_dt == HVIT_BF16)
-        hipLaunchKernelGGL((c1m_bwd_kernel<bf16_t, NCB>), dim3(blocks), dim3(THREADS), lds, st, a, (const bf16_t*)dy,
-                           sums, training, ws);
-      else
-        hipLaunchKernelGGL((c1m_bwd_kernel<float, NCB>), dim3(blocks), dim3(THREADS), lds, st, a, (const float*)dy,
-                           sums, training, ws);
+      auto launch = [&](auto td, auto fullc) {  // (FULL is built for bf16 dy only)
+        using TD = decltype(td);
+        hipLaunchKernelGGL((c1m_bwd_kernel<TD, NCB, decltype(fullc)::value>), dim3(blocks), dim3(THREADS), lds, st, a,
+                           (const TD*)dy, sums, training, ws);
+      };
+      if (dy_dt == HVIT_BF16 && full) launch(bf16_t(), std::true_type());
+      else with_elem(dy_dt, [&](auto td) { launch(td, std::false_type()); });
     });
     HVIT_LAUNCH_CHECK();
     return hvit_sum_slabs(ws, blocks, (long long)C * 9, dw_packed, stream);
@@ -1161,18 +972,14 @@ extern "C" int hvit_c1block_bwd(int dt, const hvit_conv_geom_t* g, const void* w
     constexpr int CC = decltype(ccc)::value;
     with_pool(pool, [&](auto pc) {
       constexpr int P = decltype(pc)::value;
-      if (dt == HVIT_BF16 && dy_dt == HVIT_BF16)
-        hipLaunchKernelGGL((c1_bwd_kernel<bf16_t, bf16_t, P, CV, CC>), dim3(blocks), dim3(THREADS), lds, st, a,
-                           (const bf16_t*)dy, sums, training, ws);
-      else if (dt == HVIT_BF16)
-        hipLaunchKernelGGL((c1_bwd_kernel<bf16_t, float, P, CV, CC>), dim3(blocks), dim3(THREADS), lds, st, a,
-                           (const float*)dy, sums, training, ws);
-      else if (dy_dt == HVIT_BF16)
-        hipLaunchKernelGGL((c1_bwd_kernel<float, bf16_t, P, CV, CC>), dim3(blocks), dim3(THREADS), lds, st, a,
-                           (const bf16_t*)dy, sums, training, ws);
-      else
-        hipLaunchKernelGGL((c1_bwd_kernel<float, float, P, CV, CC>), dim3(blocks), dim3(THREADS), lds, st, a,
-                           (const float*)dy, sums, training, ws);
+      with_elem(dt, [&](auto t) {
+        with_elem(dy_dt, [&](auto td) {
+          using T = decltype(t);
+          using TD = decltype(td);
+          hipLaunchKernelGGL((c1_bwd_kernel<T, TD, P, CV, CC>), dim3(blocks), dim3(THREADS), lds, st, a,
+                             (const TD*)dy, sums, training, ws);
+        });
+      });
     });
   };
   switch (C / CV) {

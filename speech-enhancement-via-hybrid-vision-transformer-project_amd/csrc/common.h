@@ -157,6 +157,25 @@ static inline DropArgs drop_args(const hvit_dropout_t* d) {
   return {d ? drop_threshold(d->p) : 0u, (d && d->p > 0.f) ? 1.f / (1.f - d->p) : 1.f, dseed(d), d ? d->site : 0u};
 }
 
+// Dropout2d of the BatchNorm tails (bnact.hip, c1block.hip: one multiplier per
+// (sample, channel)): the key is hashed on the host; a kernel re-hashes it at
+// entry only when a device seed word is present (one scalar load)
+struct DropKey {
+  uint32_t thr;  // 16-bit keep threshold, 0 = no dropout
+  float dscale;  // 1 / (1 - p)
+  uint32_t key;  // rng_key(seed, site) (host-resolved when seedp is NULL)
+  const unsigned long long* seedp;  // device seed word (hvit_dropout_t.seed_ptr)
+  unsigned long long seed;
+  uint32_t site;
+  __device__ __forceinline__ void resolve() {
+    if (seedp && thr) key = rng_key(seed ^ *seedp, site);
+  }
+};
+static inline DropKey drop_key(const hvit_dropout_t* d) {
+  const DropArgs a = drop_args(d);
+  return {a.thr, a.dscale, d ? rng_key(d->seed, d->site) : 0u, a.seed.p, a.seed.s, a.site};
+}
+
 // ----------------------------------------------------------------- GELU(erf) --
 // GELU (erf form, as torch.nn.GELU()) without the branchy libm erff: erf by
 // Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7), one rcp + one exp; the same
@@ -226,6 +245,14 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// fn(T()) with T = float or bf16_t for a runtime dtype: one launch line per
+// kernel template instead of a ladder of its instantiations
+template <typename F>
+static inline void with_elem(int dt, F&& fn) {
+  if (dt == HVIT_BF16) fn(bf16_t());
+  else fn(float());
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

@@ -16,6 +16,7 @@
 // the staging barrier) and how it rounds them (the ring kernels hand in an f32
 // h rounded to bf16, gemm_kernel the exact f32) stays that kernel's choice.
 #pragma once
+#include "chan_vec.h"  // pack4 / unpack4 / pack8 / unpack8
 #include "common.h"
 
 namespace hvit {
@@ -133,31 +134,6 @@ __device__ __forceinline__ void epi_side(const Epi& ep) {
     if (k < ep.sj_splits) s0 += src[(long)k * st + i];
     dst[i] = s0 + s1;
   }
-}
-
-// bf16 <-> f32 on 4 / 8 adjacent values (round to nearest even on the way down)
-__device__ __forceinline__ uint2 pack4(const f32x4& v) {
-  uint2 u;
-  u.x = f2bf2(v[0], v[1]);
-  u.y = f2bf2(v[2], v[3]);
-  return u;
-}
-__device__ __forceinline__ f32x4 unpack4(uint32_t lo, uint32_t hi) {
-  return (f32x4){__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u), __uint_as_float(hi << 16),
-                 __uint_as_float(hi & 0xffff0000u)};
-}
-__device__ __forceinline__ f32x4 unpack4(const uint2& u) { return unpack4(u.x, u.y); }
-__device__ __forceinline__ u32x4 pack8(const f32x4& a, const f32x4& b) {
-  u32x4 u;
-  u[0] = f2bf2(a[0], a[1]);
-  u[1] = f2bf2(a[2], a[3]);
-  u[2] = f2bf2(b[0], b[1]);
-  u[3] = f2bf2(b[2], b[3]);
-  return u;
-}
-__device__ __forceinline__ void unpack8(const u32x4& u, f32x4& a, f32x4& b) {
-  a = unpack4(u[0], u[1]);
-  b = unpack4(u[2], u[3]);
 }
 
 // 4 adjacent output columns (n .. n+nv-1) of row m: store helpers and the

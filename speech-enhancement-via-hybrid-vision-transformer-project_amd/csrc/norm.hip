@@ -14,6 +14,7 @@
 // Backward recomputes the pre-pool activations from z to route the pooled
 // gradient to the first maximum of each window (torch's tie rule), then a
 // reduce pass (sum g, sum g*xhat per channel) and an apply pass.
+#include "chan_vec.h"
 #include "common.h"
 
 namespace hvit {
@@ -100,17 +101,6 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 __host__ __device__ constexpr int lnb_rpw(int) { return 2; }
 static inline int lnb_rows(int D) { return 4 * lnb_rpw(D); }
 
-template <typename TD>
-__device__ __forceinline__ f32x4 load_row4(const TD* p) {
-  if constexpr (sizeof(TD) == 4) {
-    return *(const f32x4*)p;
-  } else {
-    const uint2 u = *(const uint2*)p;
-    return (f32x4){__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                   __uint_as_float(u.y & 0xffff0000u)};
-  }
-}
-
 // Dropout (+ DropPath row scale) of the LayerNorm input gradient, fused into
 // the backward (DROP): g = dx * keep(row * D + c) / (1 - p) * rowscale[row /
 // rps] in g's dtype, and the column sums of g (the bias gradient of the GEMM
@@ -171,7 +161,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TD* __restrict__ dy, 
       const int c = lane * 4 + i * 256;
       if (c < D) {
         xv[r][i] = *(const f32x4*)(x + (long)row * D + c);
-        dv[r][i] = load_row4<TD>(dy + (long)row * D + c);
+        dv[r][i] = load_chan4(dy + (long)row * D + c);
         rv[r][i] = resid ? *(const f32x4*)(resid + (long)row * D + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
       } else {
         xv[r][i] = dv[r][i] = rv[r][i] = (f32x4){0.f, 0.f, 0.f, 0.f};

@@ -10,41 +10,10 @@
 // points when the geometry matches (3x3, stride 1, pad 1).
 #include <algorithm>
 
+#include "chan_vec.h"
 #include "common.h"
 
 namespace hvit {
-
-template <typename T>
-struct Vec8 {  // 8 consecutive elements as floats (16 B for bf16, 32 B for f32)
-  __device__ __forceinline__ static void load(const T* p, float* f) {
-    if constexpr (sizeof(T) == 2) {
-      u32x4 u = *(const u32x4*)p;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(u[i] << 16);
-        f[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
-      }
-    } else {
-      f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        f[i] = a[i];
-        f[4 + i] = b[i];
-      }
-    }
-  }
-  __device__ __forceinline__ static void store(T* p, const float* f) {
-    if constexpr (sizeof(T) == 2) {
-      u32x4 u;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) u[i] = (uint32_t)f2bf(f[2 * i]) | ((uint32_t)f2bf(f[2 * i + 1]) << 16);
-      *(u32x4*)p = u;
-    } else {
-      *(f32x4*)p = (f32x4){f[0], f[1], f[2], f[3]};
-      *(f32x4*)(p + 4) = (f32x4){f[4], f[5], f[6], f[7]};
-    }
-  }
-};
 
 constexpr int TC_PIX = 64;   // pixels per stats tile (= BN partial tile rows)
 constexpr int TC_TILES = 16;  // tiles per block
@@ -153,7 +122,7 @@ __global__ __launch_bounds__(256) void c1_fwd_kernel(const T* __restrict__ x, co
       for (int t = 0; t < 9; ++t) acc += xv[t] * wr[t][e];
       o[e] = acc;
     }
-    if (z) Vec8<TO>::store(z + (size_t)p * Cout + cc * 8, o);  // null: statistics only (c1block.hip)
+    if (z) store_chan<8>(z + (size_t)p * Cout + cc * 8, o);  // null: statistics only (c1block.hip)
     cnt += 1.f;
     const float inv = __builtin_amdgcn_rcpf(cnt);
 #pragma unroll
@@ -214,34 +183,6 @@ __host__ __device__ inline int c1w_pix(long P) {
 }
 constexpr int C1_WG_PF = 8;    // dz prefetch depth (pixels per thread)
 
-// 8 consecutive elements kept raw in registers until used
-template <typename T>
-struct Raw8 {
-  u32x4 u;
-  __device__ __forceinline__ void load(const T* p) { u = *(const u32x4*)p; }
-  __device__ __forceinline__ void to_f(float* f) const {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[2 * i] = __uint_as_float(u[i] << 16);
-      f[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
-    }
-  }
-};
-template <>
-struct Raw8<float> {
-  f32x4 a, b;
-  __device__ __forceinline__ void load(const float* p) {
-    a = *(const f32x4*)p;
-    b = *(const f32x4*)(p + 4);
-  }
-  __device__ __forceinline__ void to_f(float* f) const {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f[i] = a[i];
-      f[4 + i] = b[i];
-    }
-  }
-};
 constexpr int WG_PIX_O1 = 256; // Cout = 1 wgrad (131k pixels at B=32)
 // CC = Cout / 8 is a template parameter so the lane reductions below unroll
 // (a runtime-bounded shuffle loop serialised 72 x 3 ds_bpermute round trips)
@@ -270,7 +211,7 @@ __global__ __launch_bounds__(256) void c1_wgrad_kernel(const T* __restrict__ x, 
   // latency-bound at this occupancy
   PixCursor pc(pbeg + pl, H, W);
   int p = pbeg + pl;
-  Raw8<T> q[C1_WG_PF];
+  ChanVec<T, 8> q[C1_WG_PF];
 #pragma unroll
   for (int k = 0; k < C1_WG_PF; ++k)
     if (p + k * lanes < pend) q[k].load(dz + (size_t)(p + k * lanes) * Cout + cc * 8);
@@ -279,7 +220,7 @@ __global__ __launch_bounds__(256) void c1_wgrad_kernel(const T* __restrict__ x, 
     for (int k = 0; k < C1_WG_PF; ++k) {
       if (p >= pend) break;
       float d[8];
-      q[k].to_f(d);
+      q[k].get(d);
       const int pn = p + C1_WG_PF * lanes;
       if (pn < pend) q[k].load(dz + (size_t)pn * Cout + cc * 8);
       float xv[9];
@@ -332,7 +273,7 @@ __global__ __launch_bounds__(256) void o1_fwd_kernel(const T* __restrict__ x, co
       const float* wt = sm + t * C;
       for (int c = 0; c < C; c += 8) {
         float v[8];
-        Vec8<T>::load(src + c, v);
+        load_chan<8>(src + c, v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) s += v[e] * wt[c + e];
       }
@@ -377,7 +318,7 @@ __global__ __launch_bounds__(256) void o1_fwd_strip_kernel(const bf16_t* __restr
   constexpr int G = 256 / CC;
   float wr[9][8];  // w packed [tap][ci]: this thread's chunk
 #pragma unroll
-  for (int t = 0; t < 9; ++t) Vec8<bf16_t>::load(w + t * C + cc * 8, wr[t]);
+  for (int t = 0; t < 9; ++t) load_chan<8>(w + t * C + cc * 8, wr[t]);
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the strip
   __syncthreads();
   const bf16_t* xs = (const bf16_t*)o1s;
@@ -394,7 +335,7 @@ __global__ __launch_bounds__(256) void o1_fwd_strip_kernel(const bf16_t* __restr
       const bool ok = (dy < 0 ? up : dy > 0 ? dn : true) && (dx < 0 ? lf : dx > 0 ? rt : true);
       if (!ok) continue;
       float v[8];
-      Vec8<bf16_t>::load(c + (dy * W + dx) * C, v);
+      load_chan<8>(c + (dy * W + dx) * C, v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) s += v[e] * wr[t][e];
     }
@@ -432,7 +373,7 @@ __global__ __launch_bounds__(256) void o1_dgrad_kernel(const TD* __restrict__ dz
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] += d * sm[t * C + cc * 8 + e];
     }
-    Vec8<T>::store(du + (size_t)q * C + cc * 8, o);
+    store_chan<8>(du + (size_t)q * C + cc * 8, o);
   }
 }
 
@@ -477,7 +418,7 @@ __global__ __launch_bounds__(256) void o1_dgrad_strip_kernel(const bf16_t* __res
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] += d * wr[t][e];
     }
-    Vec8<bf16_t>::store(du + (size_t)q * C + cc * 8, o);
+    store_chan<8>(du + (size_t)q * C + cc * 8, o);
   }
 }
 
@@ -506,7 +447,7 @@ __global__ __launch_bounds__(256) void o1_wgrad_kernel(const T* __restrict__ x, 
       const int iy = yy + t / 3 - 1, ix = xx + t % 3 - 1;
       if (iy < 0 || ix < 0 || iy >= H || ix >= W) continue;
       float v[8];
-      Vec8<T>::load(x + ((size_t)(n * Hs + iy / U) * Ws + ix / U) * C + cc * 8, v);
+      load_chan<8>(x + ((size_t)(n * Hs + iy / U) * Ws + ix / U) * C + cc * 8, v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) acc[t][e] += d * v[e];
     }
@@ -581,7 +522,7 @@ __global__ __launch_bounds__(256) void o1_wgrad_strip_kernel(const T* __restrict
       const bool ok = (dy < 0 ? up : dy > 0 ? dn : true) && (dx < 0 ? lf : dx > 0 ? rt : true);
       if (!ok) continue;
       float v[8];
-      Vec8<T>::load(c + (dy * W + dx) * C, v);
+      load_chan<8>(c + (dy * W + dx) * C, v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) acc[t][e] += d * v[e];
     }

@@ -669,10 +669,14 @@ def test_bn_finalize_vs_torch(hv, M, C, tr):
     for o in outs[1:]:
         assert all(torch.equal(a, b) for a, b in zip(o, outs[0]))
 
-@pytest.mark.parametrize("dt", ["f32", "bf16"])
-@pytest.mark.parametrize("N,H,W,C,pool,p", [(2, 32, 32, 64, 2, 0.0), (3, 15, 17, 16, 2, 0.3),
-                                            (2, 16, 16, 256, 1, 0.1), (1, 8, 8, 8, 1, 0.0)])
-def test_bn_act(hv, dt, N, H, W, C, pool, p):
+BN_ACT_SHAPES = [(2, 32, 32, 64, 2, 0.0), (3, 15, 17, 16, 2, 0.3), (2, 16, 16, 256, 1, 0.1), (1, 8, 8, 8, 1, 0.0)]
+
+
+def bn_act_check(hv, dt, N, H, W, C, pool, p, io="f32", training=1, word=None):
+    """hvit_bn_act_fwd / _bwd against torch.  io: dtype of y and dy ("same": z's
+    dtype, the 16-byte vector store / load); training 0: the eval-mode backward
+    (statistics are constants); word: a device seed word, the mask then being
+    keep_mask(seed ^ word, ...)."""
     l = L(hv)
     torch.manual_seed(N * 1000 + C + pool)
     # |z| >= 0.05: two distinct (bf16) inputs of a pooling window then differ by
@@ -683,32 +687,46 @@ def test_bn_act(hv, dt, N, H, W, C, pool, p):
     zr = z.clone().requires_grad_(True)
     gamma = (torch.rand(C, device=DEV) + 0.5).requires_grad_(True)
     beta = (torch.randn(C, device=DEV) * 0.3).requires_grad_(True)
-    m = zr.mean((0, 2, 3))
-    v = zr.var((0, 2, 3), unbiased=False)
-    bn = (zr - m[None, :, None, None]) * (v[None, :, None, None] + 1e-5).rsqrt()
-    y = F.relu(bn * gamma[None, :, None, None] + beta[None, :, None, None])
+    if training:
+        m = zr.mean((0, 2, 3))
+        v = zr.var((0, 2, 3), unbiased=False)
+        bn = (zr - m[None, :, None, None]) * (v[None, :, None, None] + 1e-5).rsqrt()
+        y = F.relu(bn * gamma[None, :, None, None] + beta[None, :, None, None])
+    else:
+        m = z.mean((0, 2, 3))
+        v = z.var((0, 2, 3), unbiased=False)
+        y = F.relu(F.batch_norm(zr, m, v, gamma, beta, training=False, eps=1e-5))
+    seed, site = 31, 9
     mask = torch.ones(N, C, device=DEV)
     if p > 0:
-        mask = torch.as_tensor(keep_mask(31, 9, N * C, p).reshape(N, C), device=DEV).float() / (1 - p)
+        mseed = seed if word is None else seed ^ word
+        mask = torch.as_tensor(keep_mask(mseed, site, N * C, p).reshape(N, C), device=DEV).float() / (1 - p)
     y = y * mask[:, :, None, None]
     if pool > 1:
         y = F.max_pool2d(y, pool)
     dtc = l.F32 if dt == "f32" else l.BF16
+    iot, ioc = (torch.float32, l.F32) if io == "f32" else (tdt(dt), dtc)
     za = nhwc(z).to(tdt(dt))
     mean = m.detach().contiguous()
     inv = (v.detach() + 1e-5).rsqrt().contiguous()
-    out = torch.empty(N, H // pool, W // pool, C, device=DEV)
-    dr = l.dropout(p, 31, 9)
+    out = torch.empty(N, H // pool, W // pool, C, device=DEV, dtype=iot)
+    seed_t = None if word is None else torch.tensor([word], dtype=torch.int64, device=DEV)
+    dr = l.dropout(p, seed, site, seed_t)
     l.call("hvit_bn_act_fwd", dtc, za.data_ptr(), N, H, W, C, mean.data_ptr(), inv.data_ptr(), gamma.data_ptr(),
-           beta.data_ptr(), dr, pool, out.data_ptr(), l.F32, s())
-    assert rel(nchw(out), y) < 1e-5
-    gy = torch.randn_like(y)
+           beta.data_ptr(), dr, pool, out.data_ptr(), ioc, s())
+    if iot == torch.float32:
+        assert rel(nchw(out), y) < 1e-5
+    else:  # one bf16 rounding of an f32 value (either neighbour)
+        yd = y.detach()
+        bound = yd.abs() * 2.0 ** -7 + 1e-5 * yd.abs().max()
+        assert int(((nchw(out.float()) - yd).abs() > bound).sum()) == 0
+    gy = torch.randn_like(y).to(iot).float()  # (a bf16 dy: rounded before the reference sees it too)
     y.backward(gy)
     dz = torch.empty(N, H, W, C, device=DEV, dtype=tdt(dt))
     sums = torch.empty(l.lib().hvit_bn_act_bwd_sums_elems(C), device=DEV)
-    gya = nhwc(gy)
+    gya = nhwc(gy).to(iot)
     l.call("hvit_bn_act_bwd", dtc, za.data_ptr(), N, H, W, C, mean.data_ptr(), inv.data_ptr(), gamma.data_ptr(),
-           beta.data_ptr(), dr, pool, gya.data_ptr(), l.F32, 1, dz.data_ptr(), dtc, sums.data_ptr(), 0, s())
+           beta.data_ptr(), dr, pool, gya.data_ptr(), ioc, training, dz.data_ptr(), dtc, sums.data_ptr(), 0, s())
     assert rel(sums[:C], beta.grad) < 1e-4
     assert rel(sums[C:2 * C], gamma.grad) < 1e-4
     err = (nchw(dz.float()) - zr.grad).abs()
@@ -717,10 +735,37 @@ def test_bn_act(hv, dt, N, H, W, C, pool, p):
         f"{int(bad.sum())} of {bad.numel()} elements off; first at {bad.nonzero()[:4].tolist()}")
     sums.zero_()  # caller-zeroed slots (HVIT_ACC_ZEROED)
     l.call("hvit_bn_act_bwd", dtc, za.data_ptr(), N, H, W, C, mean.data_ptr(), inv.data_ptr(), gamma.data_ptr(),
-           beta.data_ptr(), dr, pool, gya.data_ptr(), l.F32, 1, dz.data_ptr(), dtc, sums.data_ptr(), l.ACC_ZEROED,
-           s())
+           beta.data_ptr(), dr, pool, gya.data_ptr(), ioc, training, dz.data_ptr(), dtc, sums.data_ptr(),
+           l.ACC_ZEROED, s())
     assert rel(sums[:C], beta.grad) < 1e-4
     assert rel(sums[C:2 * C], gamma.grad) < 1e-4
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("N,H,W,C,pool,p", BN_ACT_SHAPES)
+def test_bn_act(hv, dt, N, H, W, C, pool, p):
+    bn_act_check(hv, dt, N, H, W, C, pool, p)
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("N,H,W,C,pool,p", BN_ACT_SHAPES)
+def test_bn_act_io_in_z_dtype(hv, dt, N, H, W, C, pool, p):
+    """y stored and dy loaded in z's dtype: the 16-byte vector store / load."""
+    bn_act_check(hv, dt, N, H, W, C, pool, p, io="same")
+
+
+@pytest.mark.parametrize("io", ["f32", "same"])
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("N,H,W,C,pool,p", BN_ACT_SHAPES)
+def test_bn_act_eval_backward(hv, dt, io, N, H, W, C, pool, p):
+    """training = 0: dz = sc * g, against F.batch_norm(training=False) on the same mean / var."""
+    bn_act_check(hv, dt, N, H, W, C, pool, p, io=io, training=0)
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_bn_act_seed_word(hv, dt):
+    """The Dropout2d mask follows the device seed word (seed ^ *seed_ptr)."""
+    bn_act_check(hv, dt, 3, 15, 17, 16, 2, 0.3, word=0x5151)
 
 
 @pytest.mark.parametrize("N,H,W,U,C1,C2", [(4, 64, 64, 2, 128, 128), (2, 32, 32, 2, 256, 0), (3, 7, 9, 3, 8, 24)])
