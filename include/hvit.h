@@ -169,7 +169,10 @@ int hvit_linear_wgrad_tk(int dt, const void* dy, const void* x, int M, int N, in
  *    LDS where it applies and measured faster, 2: wherever it applies; results
  *    are bit-identical).
  *  HVIT_TUNE_CONV_HALO_COUNT: read-only, the number of halo-resident launches
- *    so far. */
+ *    so far.
+ *  HVIT_TUNE_QKV_ATTN_FUSED: the qkv Linear and the attention forward as one
+ *    launch where hvit_qkv_mhsa_fused_used says so (1, the default), or always
+ *    as hvit_linear_fwd + hvit_mhsa_fwd_kb (0); results are bit-identical. */
 enum {
   HVIT_TUNE_RING = 0,
   HVIT_TUNE_C1_MFMA = 1,
@@ -177,7 +180,8 @@ enum {
   HVIT_TUNE_FP8_FWD = 5,
   HVIT_TUNE_WGRAD_GROUP = 7,
   HVIT_TUNE_CONV_HALO = 9,
-  HVIT_TUNE_CONV_HALO_COUNT = 10
+  HVIT_TUNE_CONV_HALO_COUNT = 10,
+  HVIT_TUNE_QKV_ATTN_FUSED = 11
 };
 int hvit_gemm_tune(int what, int value);
 /* Diagnostics (tests): the LDS byte offset of the 16-byte channel chunk `chunk`
@@ -313,6 +317,19 @@ long long hvit_mhsa_bias_rows(int dt, int B, int N, int H, int hd);
 int hvit_mhsa_bwd_db(int dt, const void* qkv, const void* o, const void* dout, const float* lse, int B, int N, int H,
                      int hd, float scale, const hvit_dropout_t* dropout, const unsigned* keep_bits, void* dqkv,
                      float* delta_ws, float* dbias_rows, void* stream);
+/* The qkv Linear (attention.py:55) and the attention forward in one launch:
+ * qkv = x[B*N, D] w[3D, D]^T + bias (D = H * hd), then hvit_mhsa_fwd_kb on it,
+ * one workgroup per (b, h) computing that head's q, k and v and handing them
+ * over in LDS (csrc/qkv_attention.hip).  bf16, hd = 64, N = 256, D % 64 == 0:
+ * hvit_qkv_mhsa_fused_used(dt, N, hd, D) is 1 exactly where the kernel exists
+ * and HVIT_TUNE_QKV_ATTN_FUSED is on; anywhere else this entry is an error and
+ * the caller takes the two launches.  qkv (nullable: no backward will read
+ * it), o, lse and keep_bits (nullable) receive bit for bit what
+ * hvit_linear_fwd + hvit_mhsa_fwd_kb write. */
+int hvit_qkv_mhsa_fused_used(int dt, int N, int hd, int D);
+int hvit_qkv_mhsa_fwd(int dt, const void* x, const void* w, const float* bias, int B, int N, int H, int hd,
+                      float scale, const hvit_dropout_t* dropout, void* qkv, void* o, float* lse, unsigned* keep_bits,
+                      void* stream);
 /* fp8 (OCP e4m3) forward of the same core for BASELINE config 5: bf16 qkv / o,
  * per-(b, h) power-of-two scales for K and V and per-query scales for Q
  * (e4m3 range from the absolute maxima), QK^T on v_mfma_f32_16x16x32_fp8_fp8,

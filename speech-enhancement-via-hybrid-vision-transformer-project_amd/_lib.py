@@ -22,6 +22,7 @@ ACC_DEFER = 2
 # hvit_gemm_tune knobs (include/hvit.h: HVIT_TUNE_*)
 TUNE_RING, TUNE_C1_MFMA, TUNE_ATTN_BWD, TUNE_FP8_FWD, TUNE_WGRAD_GROUP, TUNE_CONV_HALO, TUNE_CONV_HALO_COUNT = (
     0, 1, 4, 5, 7, 9, 10)
+TUNE_QKV_ATTN_FUSED = 11
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HVIT_LIB selects an alternative in-tree build (kernel A/B benchmarking only)
@@ -132,6 +133,8 @@ _SIGS = {
     "hvit_mhsa_keep_bits_elems": ([i32, i32, i32], i64),
     "hvit_mhsa_keep_bits_used": ([i32, i32, i32], i32),
     "hvit_mhsa_fwd_kb": ([i32, vp, i32, i32, i32, i32, f32, P(Dropout), vp, vp, vp, vp], i32),
+    "hvit_qkv_mhsa_fused_used": ([i32, i32, i32, i32], i32),
+    "hvit_qkv_mhsa_fwd": ([i32, vp, vp, vp, i32, i32, i32, i32, f32, P(Dropout), vp, vp, vp, vp, vp], i32),
     "hvit_mhsa_bwd_kb": ([i32, vp, vp, vp, vp, i32, i32, i32, i32, f32, P(Dropout), vp, vp, vp, vp], i32),
     "hvit_mhsa_bwd_db": ([i32, vp, vp, vp, vp, i32, i32, i32, i32, f32, P(Dropout), vp, vp, vp, vp, vp], i32),
     "hvit_layernorm_fwd": ([vp, vp, vp, i32, i32, f32, vp, i32, vp, vp, vp], i32),

@@ -4,6 +4,8 @@
 // and its fragment reads, the MFMA -> VALU hazard pad, the keep-bit layout, the
 // forward's dropout step, the key-major backward tile and the small row pieces.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace hvit {
@@ -246,6 +248,148 @@ __device__ __forceinline__ void v2_store_row(bf16_t* row, const f32x4 (&acc)[4],
     u.x = f2bf2(acc[t][0] * mul, acc[t][1] * mul);
     u.y = f2bf2(acc[t][2] * mul, acc[t][3] * mul);
     *(uint2*)(row + 16 * t + 4 * fq) = u;
+  }
+}
+
+// ------------------------------------------------------- forward body ---
+// The v2 forward from the staged K / V images onwards (mhsa_fwd_v2 after its
+// staging barrier; qkv_mhsa_fwd_fused after its qkv tile is in LDS): scores,
+// softmax, dropout + keep bits, P V, the o rows and lse of this lane's query q
+// of (b, h).  qf: the query's two 16x16x32 B-operand fragments; B: the batch
+// (keep-bit chunk stride).  CH = 256 keys per softmax chunk (the
+// register-resident score block).  Every argument is a reference to the
+// caller's own variable: with by-value parameters hipcc orders the inlined
+// body differently, and mhsa_fwd_v2<16, 256, true> no longer compiles to the
+// instructions it had when this text stood in the kernel.
+template <int KMAX, bool FULL>
+__device__ __forceinline__ void v2_fwd_body(char* const& Ks, char* const& Vs, const V2Lane& LN,
+                                            const u32x4 (&qf)[2], const int& frow, const int& fq, const int& q,
+                                            const int& b, const int& h, const uint32_t& B,
+                                            bf16_t* __restrict__ const& o, float* __restrict__ const& lse,
+                                            const int& N, const int& H, const float& scale, const uint32_t& thr,
+                                            const float& dscale, const unsigned long long& seed,
+                                            const uint32_t& site, uint32_t* __restrict__ const& kbits) {
+  constexpr int CH = 256;
+  const int D = H * 64;
+  const bool qin = FULL || q < N;
+  const float c2 = scale * 1.4426950408889634f;
+  const uint64_t bh = (uint64_t)b * H + h;
+  const uint64_t BHN = (uint64_t)B * H * N;  // keep-bit chunk stride (queries)
+  const uint32_t rk = rng_key(seed, site);
+  const uint64_t qrow = (bh * N + (qin ? q : 0)) * (uint64_t)N;
+  const uint32_t hq = (uint32_t)(qrow >> 1) + 2u * (uint32_t)fq;  // dropout-hash pair index of key 0
+  // O^T[d][q] += V^T[d][keys] P^T[keys][q]   (4 d-blocks of 16)
+  f32x4 ot[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) ot[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float mxc = -INFINITY, sum = 0.f;
+  // one 256-key chunk (C0 = 0 or 256, compile time): its scores, the online
+  // softmax update, P V; its keep bits
+  auto chunk = [&](auto c0c) {
+    constexpr int c0 = decltype(c0c)::value;
+    const int nkt = FULL ? CH / 16 : (min(N - c0, CH) + 15) >> 4;  // key tiles of this chunk
+    const char* Kc = Ks + c0 * V2_ROWB;
+    const char* Vc = Vs + c0 * V2_ROWB;
+    // S^T tiles: st[j][r] = raw score(key c0 + 16j + 4fq + r, query q)
+    // (keys >= N of the last, partial tile masked to -inf).  VALU diet: the 1/sum
+    // and the dropout 1/(1-p) on the 16 outputs instead of the 64
+    // probabilities, the dropout mask a select, masking only in a partial tile.
+    f32x4 st[CH / 16];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < CH / 16; ++j) {
+      if (j < nkt) {
+        f32x4 a = {0.f, 0.f, 0.f, 0.f};
+        a = v2_mma32(v2_fragj(Kc, LN, j, 0), qf[0], a);
+        a = v2_mma32(v2_fragj(Kc, LN, j, 1), qf[1], a);
+        v2_settle(a);
+        // (this kernel's own partial-tile mask: inlined from a shared v2_mask_max, hipcc
+        // lays the branch out differently and the partial-tile forms grow,
+        // 2093 -> 2131 and 3957 -> 4084 instructions, N = 496 forward 67.4 ->
+        // 67.7 us.  In that layout hipcc pads the taken edge itself: whether the
+        // MFMA -> VALU hazard shows depends on code layout, which is why
+        // v2_settle stays whatever this branch compiles to.)
+        if (!FULL && c0 + 16 * j + 16 > N) {  // wave-uniform: only a partial last tile
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (c0 + 16 * j + 4 * fq + r >= N) a[r] = -INFINITY;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, a[r]);
+        st[j] = a;
+      }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    // raw scores kept; the scale folds into the exponent's fma (c2 > 0, so the
+    // max commutes with it).  (Round 3 measured this form run-to-run
+    // nondeterministic at the bf16-ulp level and scaled every score first: that
+    // was the missing MFMA -> VALU wait of v2_settle, not the fma.)
+    const float mnew = fmaxf(mxc, mx * c2);  // the running max in log2 units
+    if constexpr (c0 > 0) {  // online softmax: rescale what the earlier chunks accumulated
+      const float rs = __builtin_amdgcn_exp2f(mxc - mnew);
+      sum *= rs;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) ot[t] *= rs;
+    }
+    mxc = mnew;
+    float csum = 0.f;
+#pragma unroll
+    for (int j = 0; j < CH / 16; ++j) {
+      if (j < nkt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float pv = __builtin_amdgcn_exp2f(fmaf(st[j][r], c2, -mxc));
+          st[j][r] = pv;
+          csum += pv;
+        }
+      }
+    }
+    csum += __shfl_xor(csum, 16, 64);
+    csum += __shfl_xor(csum, 32, 64);
+    sum += csum;
+    // two key tiles per 16x16x32 MFMA: the B operand is this lane's P of tiles
+    // 2jp, 2jp + 1 (keys c0 + 16(2jp + e/4) + 4fq + e%4), the A operand the
+    // matching transposed reads of V.  A missing odd tile is P = 0 against
+    // staged (finite) V rows.
+    // this lane's keep-bit word pair of chunk c0/256 for the backward (kbits non-null)
+    uint32_t kb[2] = {0u, 0u};
+#pragma unroll
+    for (int jp = 0; jp < CH / 32; ++jp) {
+      if (2 * jp < nkt) {
+        f32x4 p0 = st[2 * jp];
+        f32x4 p1 = (2 * jp + 1 < nkt) ? st[2 * jp + 1] : (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (thr) {
+          uint32_t b8 = 0u;  // the pair's two nibbles
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const int j = 2 * jp + e;
+            if (j < nkt) {
+              // rng_pair(rk, qrow + c0 + 16j + 4fq) and (.. + 2) in 32 bits:
+              // qrow and the offset are even, so (qrow + off) >> 1 = qrow / 2 + off / 2
+              const uint32_t nib = v2_keep_step(rk, hq + (uint32_t)(c0 / 2 + 8 * j), thr, e ? p1 : p0);
+              b8 |= nib << (kb_nibble(j) - kb_nibble(2 * jp));
+            }
+          }
+          kb[kb_nibble(2 * jp) >> 5] |= b8 << (kb_nibble(2 * jp) & 31);
+        }
+        const u32x4 pb = v2_cat(v2_pack(p0), v2_pack(p1));
+#pragma unroll
+        for (int t = 0; t < 4; ++t) ot[t] = v2_mma32(v2_trj2(Vc, LN, 2 * jp, t), pb, ot[t]);
+      }
+    }
+    if (qin && kbits && thr)
+      *(uint2*)(kbits + kb_pair(c0 / CH, BHN, bh * N, q, fq)) = make_uint2(kb[0], kb[1]);
+  };
+  chunk(std::integral_constant<int, 0>());
+  if constexpr (KMAX > CH) {
+    if (N > CH) chunk(std::integral_constant<int, CH>());
+  }
+  if (qin) {
+    const float inv = 1.f / sum;
+    const float os = thr ? inv * dscale : inv;
+    v2_store_row(o + ((long)b * N + q) * D + h * 64, ot, os, fq);
+    if (fq == 0) lse[bh * N + q] = (mxc + log2f(sum)) * 0.6931471805599453f;
   }
 }
 

@@ -25,6 +25,7 @@ int hvit_fp8_tune(int value);          // attention_fp8.hip
 int hvit_wgrad_group_tune(int value);  // wgrad_group.hip
 int hvit_conv_halo_tune(int value);    // gemm_conv.hip
 int hvit_conv_halo_count();
+int hvit_qkv_attn_tune(int value);     // qkv_attention.hip
 
 extern "C" int hvit_gemm_tune(int what, int value) {
   switch (what) {
@@ -35,6 +36,7 @@ extern "C" int hvit_gemm_tune(int what, int value) {
     case HVIT_TUNE_WGRAD_GROUP: return hvit_wgrad_group_tune(value);
     case HVIT_TUNE_CONV_HALO: return hvit_conv_halo_tune(value);
     case HVIT_TUNE_CONV_HALO_COUNT: return hvit_conv_halo_count();
+    case HVIT_TUNE_QKV_ATTN_FUSED: return hvit_qkv_attn_tune(value);
     default: return -1;  // 2, 3, 6, 8: retired with the forms they selected, not reused
   }
 }

@@ -121,6 +121,13 @@ def _empty(shape, dt, dev):
     return torch.empty(shape, dtype=L.torch_dtype(dt), device=dev)
 
 
+def qkv_attn_fused(dt, Nt, hd, D) -> bool:
+    """hvit_qkv_mhsa_fwd runs this shape (and hvit_gemm_tune(L.TUNE_QKV_ATTN_FUSED) is on).  An older
+    in-tree build selected with HVIT_LIB (kernel A/B) has no such entry: the two launches then."""
+    used = getattr(L.lib(), "hvit_qkv_mhsa_fused_used", None)
+    return used is not None and bool(used(dt, Nt, hd, D))
+
+
 class ZSlot:
     """A zeroed f32 accumulator (atomic target) that one backward call needs:
     a slice of the forward pass's shared zero pool, or its own zeros when the
@@ -1301,15 +1308,25 @@ class ViTBlockFn(torch.autograd.Function):
         rs1, rs2 = droppath_scales(B, dpr if training else 0.0, dp_seed, dev)
         xn1, m1, r1 = _ln(x2d, n1w, n1b, dt)
         Wqkv = cast(qkvw, dt)
-        qkv = _empty((M, 3 * D), dt, dev)
-        _launch("vit_linear_fwd", 2.0 * M * 3 * D * D,
-                lambda e, st=s: call("hvit_linear_fwd", dt, xn1.data_ptr(), Wqkv.data_ptr(), qkvb.data_ptr(), M, 3 * D, D,
-                               qkv.data_ptr(), dt, e, st))
+        # the qkv Linear and the attention forward as one launch where the library has that
+        # kernel (bf16, head_dim 64, 256 tokens); with no backward to run, no qkv is kept
+        fused = not attn_fp8 and not want_probs and qkv_attn_fused(dt, Nt, hd, D)
+        qkv = None if fused and nograd else _empty((M, 3 * D), dt, dev)
+        if not fused:
+            _launch("vit_linear_fwd", 2.0 * M * 3 * D * D,
+                    lambda e, st=s: call("hvit_linear_fwd", dt, xn1.data_ptr(), Wqkv.data_ptr(), qkvb.data_ptr(), M, 3 * D,
+                                   D, qkv.data_ptr(), dt, e, st))
         o = _empty((M, D), dt, dev)
         lse = torch.empty((B, H, Nt), dtype=torch.float32, device=dev)
         kbits = None
         probs = torch.empty((B, H, Nt, Nt), dtype=torch.float32, device=dev) if want_probs else None
-        if attn_fp8 and not want_probs:
+        if fused:
+            if d_attn.p > 0 and KEEPBITS and L.lib().hvit_mhsa_keep_bits_used(dt, Nt, hd):
+                kbits = torch.empty(L.lib().hvit_mhsa_keep_bits_elems(B, Nt, H), dtype=torch.int32, device=dev)
+            _launch("qkv_attn_fwd", 2.0 * M * 3 * D * D + 4.0 * B * H * Nt * Nt * hd,
+                    lambda e, st=s: call("hvit_qkv_mhsa_fwd", dt, xn1.data_ptr(), Wqkv.data_ptr(), qkvb.data_ptr(), B, Nt,
+                                   H, hd, scale, d_attn.c(), ptr(qkv), o.data_ptr(), lse.data_ptr(), ptr(kbits), st))
+        elif attn_fp8 and not want_probs:
             # fp8 (e4m3) QK^T / PV forward (BASELINE config 5); the backward
             # below is the bf16 kernel, recomputing P from this lse and reading
             # the dropout decisions the fp8 forward kept (same keep-bit layout)
