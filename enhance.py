@@ -12,7 +12,11 @@ defaults with a warning (enhance.py:105-110); its ``model`` section feeds
 ``create_hybrid_vit`` and its ``audio`` section the enhancer's STFT settings
 (:131-138); ``--extension`` picks the files of directory mode (:160-165).
 Additions: ``--config`` (one more YAML merged on top), ``--synthetic``,
-``--precision``, ``--frontend`` and ``--batch-size``.  STFT / iSTFT on the host
+``--precision``, ``--frontend``, ``--batch-size``, ``--resample`` (a file at
+another rate than the configured one is resampled to it on the GPU instead of
+refused, and the output is written at the configured rate, as the reference
+does) and ``--keep-rate`` (single file mode: the result is resampled back and
+written at the input's rate with the input's sample count).  STFT / iSTFT on the host
 by default, on the GPU with ``--frontend device`` (directory mode then batches
 ``--batch-size`` clips per forward); the HybridViT forward on the GPU (HIP path,
 fp32 unless --precision bf16).
@@ -43,7 +47,13 @@ def main(argv=None):
     ap.add_argument("--frontend", default="host", choices=["host", "device"],
                     help="where STFT / iSTFT run: torch on the host (default) or the HIP kernels on the GPU")
     ap.add_argument("--batch-size", type=int, default=1, help="clips per forward in directory mode")
+    ap.add_argument("--resample", action="store_true",
+                    help="take files at any sample rate: resample them to the configured rate on the GPU")
+    ap.add_argument("--keep-rate", action="store_true",
+                    help="single file mode with --resample: write the result at the input file's rate and length")
     a = ap.parse_args(argv)
+    if a.keep_rate and not a.resample:
+        ap.error("--keep-rate needs --resample")
     single = a.input is not None and a.output is not None
     directory = a.input_dir is not None and a.output_dir is not None
     if a.synthetic is None and not single and not directory:
@@ -73,7 +83,7 @@ def main(argv=None):
     au = cfg.get("audio", {}) or {}
     enh = E.AudioEnhancer(model, device=a.device, sample_rate=au.get("sample_rate", 16000), n_fft=au.get("n_fft", 512),
                           hop_length=au.get("hop_length", 128), win_length=au.get("win_length", 512),
-                          frontend=a.frontend)
+                          frontend=a.frontend, resample=a.resample)
     norm = not a.no_normalize
     if a.synthetic is not None:
         torch.manual_seed(0)
@@ -84,7 +94,7 @@ def main(argv=None):
         if a.output:
             E.write_wav(a.output, out, enh.sample_rate)
     elif single:
-        enh.enhance_file(a.input, a.output, normalize=norm)
+        enh.enhance_file(a.input, a.output, normalize=norm, keep_rate=a.keep_rate)
     else:
         enh.enhance_directory(a.input_dir, a.output_dir, extension=a.extension, normalize=norm,
                               batch_size=a.batch_size)

@@ -12,7 +12,9 @@ The reference's flags (evaluate.py:27-73) with its meaning: the test pairs are
 with a warning (:79-83); the scores go to ``evaluation_results.json`` under
 ``--output-dir`` and, with ``--save-enhanced``, the enhanced clips to its
 ``enhanced`` folder.  Additions: ``--config`` (one more YAML merged on top),
-``--precision``, ``--frontend`` and ``--batch-size``.  With ``--frontend
+``--precision``, ``--frontend``, ``--batch-size`` and ``--resample`` (files at
+another rate than the configured one are resampled to it on the GPU instead of
+refused; the scores are always computed at the configured rate).  With ``--frontend
 device`` the clips are enhanced and scored on the GPU in batches of
 ``--batch-size`` (SI-SDR, SNR, SegSNR, LSD: csrc/metrics.hip); PESQ and STOI
 need the ``pesq`` / ``pystoi`` packages and read 0.0 without them.
@@ -42,6 +44,8 @@ def main(argv=None):
     ap.add_argument("--frontend", default="host", choices=["host", "device"],
                     help="where STFT / iSTFT and the metrics run: the host (default) or the HIP kernels on the GPU")
     ap.add_argument("--batch-size", type=int, default=32, help="pairs per device batch (--frontend device)")
+    ap.add_argument("--resample", action="store_true",
+                    help="take files at any sample rate: resample them to the configured rate on the GPU")
     a = ap.parse_args(argv)
     if a.batch_size < 1:
         ap.error(f"--batch-size must be at least 1, got {a.batch_size}")
@@ -70,7 +74,8 @@ def main(argv=None):
     au = cfg.get("audio", {}) or {}
     evaluator = hv.Evaluator(model, device=a.device, sample_rate=au.get("sample_rate", 16000),
                              n_fft=au.get("n_fft", 512), hop_length=au.get("hop_length", 128),
-                             win_length=au.get("win_length", 512), frontend=a.frontend, batch_size=a.batch_size)
+                             win_length=au.get("win_length", 512), frontend=a.frontend, batch_size=a.batch_size,
+                             resample=a.resample)
     print(f"Noisy directory: {noisy_dir}\nClean directory: {clean_dir}")
     enhanced_dir = output_dir / "enhanced" if a.save_enhanced else None
     results = evaluator.evaluate_dataset(noisy_dir, clean_dir, output_dir=enhanced_dir, save_enhanced=a.save_enhanced)

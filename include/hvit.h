@@ -565,6 +565,42 @@ int hvit_spec_normalize(float* mag, int B, int F, int T, const int* lengths, int
 int hvit_istft(const float* mag, const float* phasor, const float* gain, const int* lengths, int B, int F, int T,
                int hop, const float* window, int L, float* wave_out, void* stream);
 
+/* Sample-rate conversion in front of the STFT (the resampling half of
+ * librosa.load(path, sr=16000): data/dataset.py:160, inference/enhancer.py:152,
+ * evaluation/evaluator.py:135): rational-ratio polyphase FIR resampling of a
+ * ragged f32 batch with the semantics of scipy.signal.resample_poly(x, up,
+ * down, window=taps, padtype="constant").  up / down is target / orig reduced
+ * by their gcd (they must be coprime), h the 2 * half + 1 taps already
+ * multiplied by up.  For row b with len_b valid samples and Lo_b =
+ * hvit_wave_resample_out_len(len_b, up, down) = ceil(len_b * up / down):
+ *
+ *   out[b, m] = sum_k h[half + m * down - k * up] * wave[b, k]   0 <= m < Lo_b,
+ *               over 0 <= k < len_b with 0 <= half + m * down - k * up <= 2 * half
+ *   out[b, m] = 0                                                Lo_b <= m < L_out
+ *
+ * hvit_wave_resample: wave [B, L] (row stride wave_stride elements), lengths
+ *   (int32 [B], nullable: every row is L long; len_b = 0 gives an all-zero
+ *   row) -> out [B, L_out] (row stride out_stride elements; nothing outside
+ *   out[b, 0:L_out] is written, and a row's outputs at or past L_out are
+ *   dropped).  Nothing at or past wave[b, len_b] influences a result, whatever
+ *   the buffer holds there.  With lengths == NULL, L_out below
+ *   hvit_wave_resample_out_len(L, up, down) is an error.
+ *   taps_pp is h in phase-major layout [up][J], J = ceil((2 * half + 1) / up):
+ *   taps_pp[p][j] = h[p + j * up], zero past the end, so the taps of one output
+ *   (phase p = (half + m * down) mod up) are contiguous.
+ *   peak (nullable f32 [B]) = max |out[b, :]|, which the call initialises
+ *   itself (an integer maximum on the bit images: no float atomics).
+ *   The position half + m * down is computed in 64 bits.  Every output sums
+ *   its terms in ascending j with one fma each: results are bit-identical from
+ *   run to run, and row b's does not depend on B, L, the strides or the other
+ *   rows.  The call neither allocates nor synchronises (it can be captured in
+ *   a hipGraph).  A ratio whose tile input span (about 255 * down / up + J
+ *   floats) exceeds 160 KB of LDS is an error. */
+long long hvit_wave_resample_out_len(long long len, int up, int down);
+int hvit_wave_resample(const float* wave, long long wave_stride, const int* lengths, int B, int L, int up, int down,
+                       const float* taps_pp, int half, float* out, long long out_stride, int L_out, float* peak,
+                       void* stream);
+
 /* Speech quality metrics on device waveforms and magnitudes (evaluation/metrics.py:
  * compute_sisdr :100-145, compute_snr :148-184, compute_segsnr :187-243,
  * compute_lsd :246-296).  Inputs are f32; every sum and log is f64 and the

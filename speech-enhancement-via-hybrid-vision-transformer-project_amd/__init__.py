@@ -9,6 +9,7 @@ plus the factory it forgot to export):
     FusedAdamW / clip_grad_norm_ / create_optimizer (training/optimizer.py, trainer.py:170-174),
     GraphedTrainStep (the train step replayed from a hipGraph per input shape, trainer.py:142-183),
     stft_mag / istft_mag / supported / n_frames (the device STFT / iSTFT front end, frontend.py),
+    resample_wave / resample_taps / resample_reference (sample-rate conversion on the device, resampler.py),
     compute_sisdr / compute_snr / compute_segsnr / compute_lsd / compute_pesq / compute_stoi /
     compute_all_metrics / print_metrics (evaluation/metrics.py on the host), wave_metrics / lsd /
     all_metrics_batch (the same scores on GPU batches, metrics.py) and Evaluator (evaluation/evaluator.py),
@@ -41,6 +42,7 @@ from .optim import (  # noqa: F401
 from .train_step import GraphedTrainStep  # noqa: F401
 from .config import load_all_configs, load_config, merge_configs  # noqa: F401
 from .frontend import istft_mag, n_frames, stft_mag, supported  # noqa: F401
+from .resampler import resample_reference, resample_taps, resample_wave  # noqa: F401
 from .metrics import (  # noqa: F401
     all_metrics_batch,
     compute_all_metrics,
@@ -65,7 +67,7 @@ __all__ = [
     "PositionalEncoding", "MultiHeadSelfAttention", "TransformerEncoderBlock", "VisionTransformer",
     "CombinedLoss", "create_loss_function", "FusedAdamW", "clip_grad_norm_", "create_optimizer", "GraphedTrainStep",
     "load_all_configs", "load_config", "merge_configs", "stft_mag", "istft_mag", "supported", "n_frames",
-    "compute_sisdr", "compute_snr", "compute_segsnr", "compute_lsd", "compute_pesq", "compute_stoi",
+    "resample_wave", "resample_taps", "resample_reference", "compute_sisdr", "compute_snr", "compute_segsnr", "compute_lsd", "compute_pesq", "compute_stoi",
     "compute_all_metrics", "print_metrics", "wave_metrics", "lsd", "all_metrics_batch", "Evaluator",
     "SpectrogramAugmenter", "plan_host", "apply_plan_host", "SpectrogramStore", "DeviceBatchLoader",
     "create_scheduler", "WarmupCosineScheduler", "Trainer",

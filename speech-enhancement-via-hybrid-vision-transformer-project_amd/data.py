@@ -162,18 +162,33 @@ class SpectrogramStore:
 
     @classmethod
     def from_waves(cls, noisy_list, clean_list, device, n_fft: int = N_FFT, hop: int = HOP, win: int = WIN,
-                   chunk: int = 64) -> "SpectrogramStore":
+                   chunk: int = 64, rates=None, sample_rate: int = SR) -> "SpectrogramStore":
         """Build the stores from host waveforms.  Each pair is cut to its common
         length (data/dataset.py:260-263); ``chunk`` pairs at a time go through
         frontend.stft_mag(normalize="minmax") as one ragged batch (the STFT of
         :183-190 and the per-utterance min-max of :213-219) and each clip's
-        valid frames are copied to its slot."""
+        valid frames are copied to its slot.
+
+        ``rates`` (optional, per pair a sample rate or a ``(noisy, clean)`` pair
+        of them): a clip at another rate than ``sample_rate`` is uploaded raw
+        and resampled on the device (resampler.resample_wave) before the cut
+        to the common length, so a chunk is still uploaded once."""
         from .frontend import n_frames, stft_mag
 
         if len(noisy_list) != len(clean_list) or not len(noisy_list):
             raise ValueError("hvit data: need as many noisy as clean clips, at least one")
         device = torch.device(device)
-        lens = [min(len(a), len(b)) for a, b in zip(noisy_list, clean_list)]
+        if rates is None:
+            lens = [min(len(a), len(b)) for a, b in zip(noisy_list, clean_list)]
+        else:
+            from .resampler import out_length, ratio
+
+            sr = int(sample_rate)
+            if len(rates) != len(noisy_list):
+                raise ValueError("hvit data: rates must give one entry per pair")
+            rates = [(int(r), int(r)) if np.isscalar(r) else (int(r[0]), int(r[1])) for r in rates]
+            lens = [min(out_length(len(a), *ratio(ra, sr)), out_length(len(b), *ratio(rb, sr)))
+                    for a, b, (ra, rb) in zip(noisy_list, clean_list, rates)]
         if min(lens) < 1:
             raise ValueError("hvit data: empty clip")
         frames = np.array([n_frames(n, hop) for n in lens], dtype=np.int32)
@@ -184,29 +199,64 @@ class SpectrogramStore:
         for s in range(0, len(lens), max(1, int(chunk))):
             part = range(s, min(s + max(1, int(chunk)), len(lens)))
             Lmax = max(lens[i] for i in part)
-            wave = np.zeros((2 * len(part), Lmax), dtype=np.float32)
-            for k, i in enumerate(part):
-                wave[k, :lens[i]] = np.asarray(noisy_list[i], dtype=np.float32)[:lens[i]]
-                wave[len(part) + k, :lens[i]] = np.asarray(clean_list[i], dtype=np.float32)[:lens[i]]
+            if rates is None:
+                wave = np.zeros((2 * len(part), Lmax), dtype=np.float32)
+                for k, i in enumerate(part):
+                    wave[k, :lens[i]] = np.asarray(noisy_list[i], dtype=np.float32)[:lens[i]]
+                    wave[len(part) + k, :lens[i]] = np.asarray(clean_list[i], dtype=np.float32)[:lens[i]]
+                wave = torch.from_numpy(wave).to(device)
+            else:
+                wave = cls._resampled_rows([(noisy_list[i], rates[i][0]) for i in part]
+                                           + [(clean_list[i], rates[i][1]) for i in part], sr, Lmax, device)
             ln = [lens[i] for i in part] * 2
-            mag = stft_mag(torch.from_numpy(wave).to(device), ln, n_fft, hop, win, normalize="minmax")
+            mag = stft_mag(wave, ln, n_fft, hop, win, normalize="minmax")
             for k, i in enumerate(part):
                 o, T = int(offsets[i]), int(frames[i])
                 noisy[o:o + F * T].view(F, T).copy_(mag[k, 0, :, :T])
                 clean[o:o + F * T].view(F, T).copy_(mag[len(part) + k, 0, :, :T])
         return cls(noisy, clean, frames, F)
 
+    @staticmethod
+    def _resampled_rows(rows, sr: int, Lmax: int, device) -> torch.Tensor:
+        """A chunk's device batch ``[len(rows), Lmax]`` from ``(host clip, rate)``
+        rows: one raw upload per distinct rate, resampled to ``sr`` on the
+        device and gathered into place.  A row may hold samples past the cut
+        its pair is given (stft_mag takes the lengths and ignores them)."""
+        from .resampler import resample_wave
+
+        wave = torch.zeros((len(rows), Lmax), dtype=torch.float32, device=device)
+        by_rate = {}
+        for k, (_, r) in enumerate(rows):
+            by_rate.setdefault(r, []).append(k)
+        for r, ks in sorted(by_rate.items()):
+            raw = [len(rows[k][0]) for k in ks]
+            host = np.zeros((len(ks), max(raw)), dtype=np.float32)
+            for j, k in enumerate(ks):
+                host[j, :raw[j]] = np.asarray(rows[k][0], dtype=np.float32)
+            dev_rows = torch.from_numpy(host).to(device)
+            if r != sr:
+                dev_rows = resample_wave(dev_rows, raw, r, sr)[0]
+            W = min(Lmax, dev_rows.shape[1])  # at least every member's cut
+            wave[torch.as_tensor(ks, device=device), :W] = dev_rows[:, :W]
+        return wave
+
     @classmethod
     def from_directory(cls, data_root, split: str = "train", config=None, device="cuda",
                        chunk: int = 64) -> "SpectrogramStore":
         """The split's pairs (``pair_files``) read with enhancer.read_wav and
         built with ``from_waves``; ``config`` is the reference's data config
-        (sample_rate, n_fft, hop_length, win_length, train_val_split).  Of the
+        (sample_rate, n_fft, hop_length, win_length, train_val_split) plus one
+        key of this project's own, ``resample`` (not a reference key; default
+        false): when true every file is read at its own rate
+        (enhancer.read_audio) and resampled to ``sample_rate`` on the device,
+        noisy and clean each, before the cut to the common length, as the
+        reference's librosa.load(sr=sample_rate) does; without it a file at
+        another rate raises.  Of the
         reference's waveform preprocessing (dataset.py:256-258) the default, peak
         normalisation, is a positive scale that the per-utterance min-max takes
         out again; pre-emphasis and silence trimming (off by default) are not
         implemented here and raise when the config turns them on."""
-        from .enhancer import read_wav
+        from .enhancer import read_audio, read_wav
 
         config = config or {}
         pre = config.get("preprocessing", {}) or {}
@@ -219,11 +269,19 @@ class SpectrogramStore:
         pairs = pair_files(data_root, split, config)
         if not pairs:
             raise FileNotFoundError(f"hvit data: no audio pairs for split {split!r} under {data_root}")
-        noisy = [read_wav(n, sr) for n, _ in pairs]
-        clean = [read_wav(c, sr) for _, c in pairs]
+        rates = None
+        if config.get("resample", False):
+            noisy, clean = [read_audio(n) for n, _ in pairs], [read_audio(c) for _, c in pairs]
+            rates = [(a[1], b[1]) for a, b in zip(noisy, clean)]
+            noisy, clean = [a[0] for a in noisy], [b[0] for b in clean]
+            if all(ra == sr and rb == sr for ra, rb in rates):
+                rates = None
+        else:
+            noisy = [read_wav(n, sr) for n, _ in pairs]
+            clean = [read_wav(c, sr) for _, c in pairs]
         print(f"Loaded {len(pairs)} audio pairs for {split} split")
         return cls.from_waves(noisy, clean, device, config.get("n_fft", N_FFT), config.get("hop_length", HOP),
-                              config.get("win_length", WIN), chunk)
+                              config.get("win_length", WIN), chunk, rates=rates, sample_rate=sr)
 
     @classmethod
     def synthetic(cls, n: int, seconds_range=(2.0, 4.0), seed: int = 0, device="cuda") -> "SpectrogramStore":

@@ -24,17 +24,21 @@ import torch
 import torch.nn as nn
 
 from . import metrics as M
-from .enhancer import AudioEnhancer, read_wav, write_wav
+from .enhancer import AudioEnhancer, read_audio, read_wav, write_wav
 
 
 class Evaluator:
     """evaluation/evaluator.py:27-52 plus ``frontend`` ("host" or "device"),
-    ``batch_size`` (pairs per device batch) and ``precision`` (None keeps the
-    model's; "fp32" / "bf16" sets a HybridViT's forward precision)."""
+    ``batch_size`` (pairs per device batch), ``precision`` (None keeps the
+    model's; "fp32" / "bf16" sets a HybridViT's forward precision) and
+    ``resample`` (True: a file at another rate is resampled to ``sample_rate``
+    on the device as it is loaded, noisy and clean each at its own rate, as the
+    reference's librosa.load(sr=16000) does; the metrics are always computed at
+    ``sample_rate``.  The default refuses such a file)."""
 
     def __init__(self, model: nn.Module, device: str = "cuda", sample_rate: int = 16000, n_fft: int = 512,
                  hop_length: int = 128, win_length: int = 512, frontend: str = "host", batch_size: int = 32,
-                 precision: Optional[str] = None):
+                 precision: Optional[str] = None, resample: bool = False):
         if batch_size < 1:
             raise ValueError(f"hvit evaluator: batch_size={batch_size}")
         if precision is not None:
@@ -52,14 +56,29 @@ class Evaluator:
         self.win_length = win_length
         self.frontend = frontend
         self.batch_size = int(batch_size)
+        self.resample = bool(resample)
 
     def enhance_audio(self, noisy_audio: np.ndarray) -> np.ndarray:
         """evaluator.py:54-117."""
         return self.enhancer.enhance(noisy_audio)
 
+    def _read(self, path) -> np.ndarray:
+        """One file at ``sample_rate``: refused at another rate by default;
+        with ``resample`` read at its own rate and resampled on the device."""
+        if not self.resample:
+            return read_wav(path, self.sample_rate)
+        audio, sr = read_audio(path)
+        if sr == self.sample_rate or audio.size == 0:
+            return audio
+        from .resampler import resample_wave
+
+        raw = torch.from_numpy(np.ascontiguousarray(audio))[None].to(torch.device(self.device))
+        out, _ = resample_wave(raw, [audio.size], sr, self.sample_rate)
+        return out[0].cpu().numpy()
+
     def _load_pair(self, noisy_path, clean_path):
-        noisy = read_wav(noisy_path, self.sample_rate)
-        clean = read_wav(clean_path, self.sample_rate)
+        noisy = self._read(noisy_path)
+        clean = self._read(clean_path)
         n = min(len(noisy), len(clean))
         return np.ascontiguousarray(noisy[:n]), np.ascontiguousarray(clean[:n])
 

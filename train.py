@@ -1,6 +1,7 @@
 """Training CLI (the reference's train.py).
 
     python train.py --config-dir config --data-root data/voicebank_demand
+    python train.py --config-dir config --data-root data/voicebank_demand --resample   # the 48 kHz corpus as downloaded
     python train.py --config-dir config --resume checkpoints/best_model.pth
     python train.py --synthetic 64 --epochs 2 --batch-size 8
 
@@ -13,7 +14,9 @@ set is read once, framed and normalised on the GPU and kept there
 (``DeviceBatchLoader``), the train loader with ``shuffle`` and ``drop_last``
 and the validation loader without, as at train.py:119-135.  Additions:
 ``--epochs`` and ``--batch-size`` override the config, ``--precision`` picks
-the model's arithmetic (default bf16), and ``--synthetic N`` trains on N
+the model's arithmetic (default bf16), ``--resample`` sets the data config key
+``resample`` (files at another rate than ``data.sample_rate`` are resampled to
+it on the GPU as the store is built instead of refused), and ``--synthetic N`` trains on N
 synthetic pairs (and validates on N // 4 more) so that the command runs with
 no dataset.  A missing config directory means the reference's defaults.  The
 last line printed is the best checkpoint's path.
@@ -37,6 +40,9 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=None, help="override training.batch_size")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N",
                     help="train on N synthetic pairs instead of --data-root")
+    ap.add_argument("--resample", action="store_true",
+                    help="take a corpus at any sample rate (VoiceBank-DEMAND ships at 48 kHz): resample every file "
+                         "to data.sample_rate on the GPU (sets the data config key 'resample')")
     ap.add_argument("--precision", default="bf16", choices=["fp32", "bf16"])
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--seed", type=int, default=42)
@@ -60,6 +66,8 @@ def main(argv=None):
         cfg = {}
     data_cfg = dict(cfg.get("data", {}) or {})
     train_cfg = dict(cfg.get("training", {}) or {})
+    if a.resample:
+        data_cfg["resample"] = True
     if a.epochs is not None:
         train_cfg["num_epochs"] = a.epochs
     if a.batch_size is not None:
