@@ -68,22 +68,13 @@ def main(argv=None):
     hv = hvit_amd_loader.load()
     from hvit_amd import enhancer as E
 
-    try:
-        cfg = hv.load_all_configs(a.config_dir)
-    except Exception:  # the reference's bare except (enhance.py:106-110)
-        print("Warning: Could not load config files. Using defaults.")
-        cfg = {}
-    if a.config:
-        cfg = hv.merge_configs(cfg, hv.load_config(a.config) or {})
+    cfg = hv.load_cli_configs(a.config_dir, a.config)
     model = hv.create_hybrid_vit(cfg, precision=a.precision)
     if a.checkpoint:
         model = E.load_model_for_inference(a.checkpoint, model, a.device)
     elif a.synthetic is None:
         ap.error("--checkpoint is required unless --synthetic is given")
-    au = cfg.get("audio", {}) or {}
-    enh = E.AudioEnhancer(model, device=a.device, sample_rate=au.get("sample_rate", 16000), n_fft=au.get("n_fft", 512),
-                          hop_length=au.get("hop_length", 128), win_length=au.get("win_length", 512),
-                          frontend=a.frontend, resample=a.resample)
+    enh = E.AudioEnhancer(model, device=a.device, frontend=a.frontend, resample=a.resample, **hv.audio_settings(cfg))
     norm = not a.no_normalize
     if a.synthetic is not None:
         torch.manual_seed(0)

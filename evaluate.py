@@ -55,13 +55,7 @@ def main(argv=None):
     hv = hvit_amd_loader.load()
     from hvit_amd import enhancer as E
 
-    try:
-        cfg = hv.load_all_configs(a.config_dir)
-    except Exception:  # the reference's bare except (evaluate.py:79-83)
-        print("Warning: Could not load config files. Using defaults.")
-        cfg = {}
-    if a.config:
-        cfg = hv.merge_configs(cfg, hv.load_config(a.config) or {})
+    cfg = hv.load_cli_configs(a.config_dir, a.config)
     data_root = Path(a.data_root)
     noisy_dir = Path(a.noisy_dir) if a.noisy_dir else data_root / "noisy_testset_wav"
     clean_dir = Path(a.clean_dir) if a.clean_dir else data_root / "clean_testset_wav"
@@ -71,11 +65,8 @@ def main(argv=None):
     model = hv.create_hybrid_vit(cfg, precision=a.precision)
     print(f"Loading checkpoint from {a.checkpoint}")
     model = E.load_model_for_inference(a.checkpoint, model, a.device)
-    au = cfg.get("audio", {}) or {}
-    evaluator = hv.Evaluator(model, device=a.device, sample_rate=au.get("sample_rate", 16000),
-                             n_fft=au.get("n_fft", 512), hop_length=au.get("hop_length", 128),
-                             win_length=au.get("win_length", 512), frontend=a.frontend, batch_size=a.batch_size,
-                             resample=a.resample)
+    evaluator = hv.Evaluator(model, device=a.device, frontend=a.frontend, batch_size=a.batch_size,
+                             resample=a.resample, **hv.audio_settings(cfg))
     print(f"Noisy directory: {noisy_dir}\nClean directory: {clean_dir}")
     enhanced_dir = output_dir / "enhanced" if a.save_enhanced else None
     results = evaluator.evaluate_dataset(noisy_dir, clean_dir, output_dir=enhanced_dir, save_enhanced=a.save_enhanced)

@@ -40,7 +40,7 @@ from .optim import (  # noqa: F401
     create_scheduler,
 )
 from .train_step import GraphedTrainStep  # noqa: F401
-from .config import load_all_configs, load_config, merge_configs  # noqa: F401
+from .config import audio_settings, load_all_configs, load_cli_configs, load_config, merge_configs  # noqa: F401
 from .frontend import istft_mag, n_frames, stft_mag, supported  # noqa: F401
 from .resampler import resample_reference, resample_taps, resample_wave  # noqa: F401
 from .metrics import (  # noqa: F401
@@ -66,7 +66,8 @@ __all__ = [
     "HybridViT", "create_hybrid_vit", "ConvBlock", "TransposeConvBlock", "FeedForward", "PatchEmbedding",
     "PositionalEncoding", "MultiHeadSelfAttention", "TransformerEncoderBlock", "VisionTransformer",
     "CombinedLoss", "create_loss_function", "FusedAdamW", "clip_grad_norm_", "create_optimizer", "GraphedTrainStep",
-    "load_all_configs", "load_config", "merge_configs", "stft_mag", "istft_mag", "supported", "n_frames",
+    "load_all_configs", "load_config", "merge_configs", "load_cli_configs", "audio_settings", "stft_mag", "istft_mag",
+    "supported", "n_frames",
     "resample_wave", "resample_taps", "resample_reference", "compute_sisdr", "compute_snr", "compute_segsnr", "compute_lsd", "compute_pesq", "compute_stoi",
     "compute_all_metrics", "print_metrics", "wave_metrics", "lsd", "all_metrics_batch", "Evaluator",
     "SpectrogramAugmenter", "plan_host", "apply_plan_host", "SpectrogramStore", "DeviceBatchLoader",

@@ -55,4 +55,28 @@ def load_all_configs(config_dir: Union[str, Path] = "config") -> Dict[str, Any]:
     return merged
 
 
-__all__ = ["load_config", "merge_configs", "load_all_configs"]
+def load_cli_configs(config_dir: Union[str, Path] = "config", extra: Union[str, Path, None] = None) -> Dict[str, Any]:
+    """What enhance.py and evaluate.py start from: ``load_all_configs`` with the
+    reference's fall-back and warning when that fails (its bare except,
+    enhance.py:105-110, evaluate.py:79-83), then ``extra`` (a YAML) on top."""
+    try:
+        cfg = load_all_configs(config_dir)
+    except Exception:
+        print("Warning: Could not load config files. Using defaults.")
+        cfg = {}
+    if extra:
+        cfg = merge_configs(cfg, load_config(extra) or {})
+    return cfg
+
+
+def audio_settings(cfg: Dict[str, Any]) -> Dict[str, int]:
+    """The ``audio`` section's ``sample_rate``, ``n_fft``, ``hop_length`` and
+    ``win_length`` (defaults when absent) as AudioEnhancer / Evaluator keywords."""
+    from .audio import HOP, N_FFT, SR, WIN
+
+    au = (cfg or {}).get("audio", {}) or {}
+    return {"sample_rate": au.get("sample_rate", SR), "n_fft": au.get("n_fft", N_FFT),
+            "hop_length": au.get("hop_length", HOP), "win_length": au.get("win_length", WIN)}
+
+
+__all__ = ["load_config", "merge_configs", "load_all_configs", "load_cli_configs", "audio_settings"]

@@ -8,7 +8,8 @@ win 512, periodic Hann, center=True; inference/enhancer.py:82-89,
 data/dataset.py:183-190) and per-utterance min-max scaling
 (data/dataset.py:213-219).  The framing runs on the host by default (north
 star); ``spectrogram_batch(..., device=...)`` runs it and the scaling on the GPU
-as one batch (frontend.py, csrc/stft.hip).
+as one batch (frontend.py, csrc/stft.hip).  ``SpectrogramStore.from_waves``
+builds its wave batches with audio.py, which defines ``SR`` etc.
 """
 
 from __future__ import annotations
@@ -16,8 +17,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-SR = 16000
-N_FFT, HOP, WIN = 512, 128, 512
+from .audio import HOP, N_FFT, SR, WIN, WaveBatch, out_length, read_audio, read_wav, upload_rows
 
 
 def harmonic_pair(n_samples: int, seed: int):
@@ -181,13 +181,11 @@ class SpectrogramStore:
         if rates is None:
             lens = [min(len(a), len(b)) for a, b in zip(noisy_list, clean_list)]
         else:
-            from .resampler import out_length, ratio
-
             sr = int(sample_rate)
             if len(rates) != len(noisy_list):
                 raise ValueError("hvit data: rates must give one entry per pair")
             rates = [(int(r), int(r)) if np.isscalar(r) else (int(r[0]), int(r[1])) for r in rates]
-            lens = [min(out_length(len(a), *ratio(ra, sr)), out_length(len(b), *ratio(rb, sr)))
+            lens = [min(out_length(len(a), ra, sr), out_length(len(b), rb, sr))
                     for a, b, (ra, rb) in zip(noisy_list, clean_list, rates)]
         if min(lens) < 1:
             raise ValueError("hvit data: empty clip")
@@ -200,11 +198,8 @@ class SpectrogramStore:
             part = range(s, min(s + max(1, int(chunk)), len(lens)))
             Lmax = max(lens[i] for i in part)
             if rates is None:
-                wave = np.zeros((2 * len(part), Lmax), dtype=np.float32)
-                for k, i in enumerate(part):
-                    wave[k, :lens[i]] = np.asarray(noisy_list[i], dtype=np.float32)[:lens[i]]
-                    wave[len(part) + k, :lens[i]] = np.asarray(clean_list[i], dtype=np.float32)[:lens[i]]
-                wave = torch.from_numpy(wave).to(device)
+                wave = upload_rows([noisy_list[i][:lens[i]] for i in part] + [clean_list[i][:lens[i]] for i in part],
+                                   device, width=Lmax)
             else:
                 wave = cls._resampled_rows([(noisy_list[i], rates[i][0]) for i in part]
                                            + [(clean_list[i], rates[i][1]) for i in part], sr, Lmax, device)
@@ -222,20 +217,12 @@ class SpectrogramStore:
         rows: one raw upload per distinct rate, resampled to ``sr`` on the
         device and gathered into place.  A row may hold samples past the cut
         its pair is given (stft_mag takes the lengths and ignores them)."""
-        from .resampler import resample_wave
-
         wave = torch.zeros((len(rows), Lmax), dtype=torch.float32, device=device)
         by_rate = {}
         for k, (_, r) in enumerate(rows):
             by_rate.setdefault(r, []).append(k)
         for r, ks in sorted(by_rate.items()):
-            raw = [len(rows[k][0]) for k in ks]
-            host = np.zeros((len(ks), max(raw)), dtype=np.float32)
-            for j, k in enumerate(ks):
-                host[j, :raw[j]] = np.asarray(rows[k][0], dtype=np.float32)
-            dev_rows = torch.from_numpy(host).to(device)
-            if r != sr:
-                dev_rows = resample_wave(dev_rows, raw, r, sr)[0]
+            dev_rows = WaveBatch.from_clips([rows[k][0] for k in ks], device, r, sr).wave
             W = min(Lmax, dev_rows.shape[1])  # at least every member's cut
             wave[torch.as_tensor(ks, device=device), :W] = dev_rows[:, :W]
         return wave
@@ -243,12 +230,12 @@ class SpectrogramStore:
     @classmethod
     def from_directory(cls, data_root, split: str = "train", config=None, device="cuda",
                        chunk: int = 64) -> "SpectrogramStore":
-        """The split's pairs (``pair_files``) read with enhancer.read_wav and
+        """The split's pairs (``pair_files``) read with audio.read_wav and
         built with ``from_waves``; ``config`` is the reference's data config
         (sample_rate, n_fft, hop_length, win_length, train_val_split) plus one
         key of this project's own, ``resample`` (not a reference key; default
         false): when true every file is read at its own rate
-        (enhancer.read_audio) and resampled to ``sample_rate`` on the device,
+        (audio.read_audio) and resampled to ``sample_rate`` on the device,
         noisy and clean each, before the cut to the common length, as the
         reference's librosa.load(sr=sample_rate) does; without it a file at
         another rate raises.  Of the
@@ -256,8 +243,6 @@ class SpectrogramStore:
         normalisation, is a positive scale that the per-utterance min-max takes
         out again; pre-emphasis and silence trimming (off by default) are not
         implemented here and raise when the config turns them on."""
-        from .enhancer import read_audio, read_wav
-
         config = config or {}
         pre = config.get("preprocessing", {}) or {}
         for key in ("apply_pre_emphasis", "trim_silence"):

@@ -10,7 +10,8 @@ batch is enhanced by the device front end, scored there
 (``all_metrics_batch``: enhanced and noisy against clean in one
 ``wave_metrics`` call of 2 B rows, one ``lsd`` call) and only the small table
 of scores is downloaded.  A pair is cut to its shorter member before it is
-enhanced, and ``save_enhanced`` writes the waveform that was scored.
+enhanced, and ``save_enhanced`` writes the waveform that was scored.  Files are
+read and the batches built by audio.py (``WaveBatch``, ``upload_rows``).
 """
 
 from __future__ import annotations
@@ -24,7 +25,8 @@ import torch
 import torch.nn as nn
 
 from . import metrics as M
-from .enhancer import AudioEnhancer, read_audio, read_wav, write_wav
+from .audio import HOP, N_FFT, SR, WIN, WaveBatch, read_audio, read_wav, upload_rows, write_wav
+from .enhancer import AudioEnhancer
 
 
 class Evaluator:
@@ -36,8 +38,8 @@ class Evaluator:
     reference's librosa.load(sr=16000) does; the metrics are always computed at
     ``sample_rate``.  The default refuses such a file)."""
 
-    def __init__(self, model: nn.Module, device: str = "cuda", sample_rate: int = 16000, n_fft: int = 512,
-                 hop_length: int = 128, win_length: int = 512, frontend: str = "host", batch_size: int = 32,
+    def __init__(self, model: nn.Module, device: str = "cuda", sample_rate: int = SR, n_fft: int = N_FFT,
+                 hop_length: int = HOP, win_length: int = WIN, frontend: str = "host", batch_size: int = 32,
                  precision: Optional[str] = None, resample: bool = False):
         if batch_size < 1:
             raise ValueError(f"hvit evaluator: batch_size={batch_size}")
@@ -70,11 +72,7 @@ class Evaluator:
         audio, sr = read_audio(path)
         if sr == self.sample_rate or audio.size == 0:
             return audio
-        from .resampler import resample_wave
-
-        raw = torch.from_numpy(np.ascontiguousarray(audio))[None].to(torch.device(self.device))
-        out, _ = resample_wave(raw, [audio.size], sr, self.sample_rate)
-        return out[0].cpu().numpy()
+        return WaveBatch.from_clips([audio], self.device, sr, self.sample_rate).rows()[0]
 
     def _load_pair(self, noisy_path, clean_path):
         noisy = self._read(noisy_path)
@@ -91,13 +89,10 @@ class Evaluator:
         """One batch of pairs with one frame count: a list of metric dicts and
         the enhanced batch ``[B, Lmax]`` on the device."""
         n = len(noisy_clips)
-        enhanced, ln = self.enhancer._enhance_device_tensor(noisy_clips, True)
-        ref = np.zeros((2 * n, enhanced.shape[1]), dtype=np.float32)
-        for r, (nz, c) in enumerate(zip(noisy_clips, clean_clips)):
-            ref[r, :c.size] = c
-            ref[n + r, :nz.size] = nz
-        ref = torch.from_numpy(ref).to(enhanced.device)
-        scores = M.all_metrics_batch(ref[:n], enhanced, ref[n:], ln)
+        batch = WaveBatch.from_clips(noisy_clips, self.device, self.sample_rate, self.sample_rate, peak=True)
+        enhanced = self.enhancer._enhance_device_tensor(batch, True)
+        ref = upload_rows(clean_clips + noisy_clips, enhanced.device, width=enhanced.shape[1])
+        scores = M.all_metrics_batch(ref[:n], enhanced, ref[n:], batch.lengths)
         names = list(scores)
         table = torch.stack([scores[k] for k in names]).cpu().numpy()  # the batch's one download
         return [{k: float(table[j, r]) for j, k in enumerate(names)} for r in range(n)], enhanced

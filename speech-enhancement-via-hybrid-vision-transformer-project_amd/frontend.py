@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._args import canonical_device, lengths_arg, wave_arg
 
 N_FFTS = (256, 512, 1024)
 _MODES = {None: None, "max": 0, "minmax": 1}
@@ -48,9 +49,7 @@ def _check(n_fft, hop_length, win_length):
 def window_table(n_fft: int, win_length: int, device) -> torch.Tensor:
     """The periodic Hann window of win_length centred in n_fft, computed in
     float64 and rounded once; cached per device and setting."""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = canonical_device(device)
     key = (str(device), n_fft, win_length)
     w = _windows.get(key)
     if w is None:
@@ -67,17 +66,6 @@ def _need_gpu(t: torch.Tensor, what: str):
         raise RuntimeError(f"hvit frontend: {what} must be a GPU tensor; there is no CPU path")
 
 
-def _lengths_arg(lengths, B: int, device) -> Optional[torch.Tensor]:
-    if lengths is None:
-        return None
-    if not isinstance(lengths, torch.Tensor):
-        lengths = torch.as_tensor(np.asarray(lengths, dtype=np.int32))
-    lengths = lengths.to(device=device, dtype=torch.int32).contiguous()
-    if lengths.shape != (B,):
-        raise ValueError(f"hvit frontend: lengths must have shape ({B},), got {tuple(lengths.shape)}")
-    return lengths
-
-
 def stft_mag(wave: torch.Tensor, lengths=None, n_fft: int = 512, hop_length: int = 128, win_length: int = 512,
              return_phasor: bool = False, normalize: Optional[str] = None):
     """Magnitude spectrograms [B, 1, F, T] of a float32 GPU batch ``wave``
@@ -88,21 +76,13 @@ def stft_mag(wave: torch.Tensor, lengths=None, n_fft: int = 512, hop_length: int
     frames.  With ``return_phasor`` the result is ``(mag, phasor [B, F, T, 2],
     stats [B, 2])``; stats holds each row's min and max of the magnitude BEFORE
     normalisation.  Frames past a row's ``1 + len // hop`` are 0 / (1, 0)."""
-    if not isinstance(wave, torch.Tensor):
-        raise TypeError("hvit frontend: wave must be a torch.Tensor")
-    _need_gpu(wave, "wave")
+    wave, B, Ln, row_stride = wave_arg(wave, "hvit frontend", "wave")
     _check(n_fft, hop_length, win_length)
     if normalize not in _MODES:
         raise ValueError(f"hvit frontend: normalize={normalize!r} (None, 'max' or 'minmax')")
-    if wave.dim() != 2 or wave.dtype != torch.float32 or wave.shape[1] < 1 or wave.shape[0] < 1:
-        raise ValueError(f"hvit frontend: wave must be float32 [B, L], got {wave.dtype} {tuple(wave.shape)}")
-    B, Ln = wave.shape
-    if wave.stride(1) != 1 or (B > 1 and wave.stride(0) < Ln):
-        wave = wave.contiguous()
-    row_stride = wave.stride(0) if B > 1 else Ln  # a single row's stride is arbitrary (0 for a broadcast view)
     dev = wave.device
     F, T = n_fft // 2 + 1, n_frames(Ln, hop_length)
-    lens = _lengths_arg(lengths, B, dev)
+    lens = lengths_arg(lengths, B, dev, "hvit frontend")
     win = window_table(n_fft, win_length, dev)
     mag = torch.empty((B, 1, F, T), dtype=torch.float32, device=dev)
     phasor = torch.empty((B, F, T, 2), dtype=torch.float32, device=dev) if return_phasor else None
@@ -144,7 +124,7 @@ def istft_mag(mag: torch.Tensor, phasor: torch.Tensor, lengths_or_length: Union[
     else:
         if length is None:
             length = int(torch.as_tensor(lengths_or_length).max())
-        lens, Ln = _lengths_arg(lengths_or_length, B, dev), int(length)
+        lens, Ln = lengths_arg(lengths_or_length, B, dev, "hvit frontend"), int(length)
     if Ln < 1:
         raise ValueError(f"hvit frontend: output length {Ln}")
     if gain is not None:

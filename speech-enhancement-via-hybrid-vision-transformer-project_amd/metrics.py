@@ -30,6 +30,7 @@ import torch
 
 from . import _lib as L
 from . import frontend as FE
+from ._args import lengths_arg, wave_arg
 
 _warned = set()
 
@@ -164,17 +165,14 @@ def print_metrics(metrics: Dict[str, float], title: str = "Metrics") -> None:
 
 # ------------------------------------------------------------------ device --
 
-def _wave_arg(t, what: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"hvit metrics: {what} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"hvit metrics: {what} must be a GPU tensor; there is no CPU path")
-    if t.dim() != 2 or t.dtype != torch.float32 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"hvit metrics: {what} must be float32 [B, L], got {t.dtype} {tuple(t.shape)}")
-    B, Ln = t.shape
-    if t.stride(1) != 1 or (B > 1 and t.stride(0) < Ln):
-        t = t.contiguous()
-    return t
+def _pair_arg(clean, est):
+    """``(clean, est, B, L, row strides)`` of two batches of one shape and device."""
+    clean, B, Ln, cs = wave_arg(clean, "hvit metrics", "clean")
+    est, _, _, es = wave_arg(est, "hvit metrics", "est")
+    if clean.shape != est.shape or clean.device != est.device:
+        raise ValueError(f"hvit metrics: clean {tuple(clean.shape)} on {clean.device} and est {tuple(est.shape)} on "
+                         f"{est.device} must match")
+    return clean, est, B, Ln, cs, es
 
 
 def _lengths(lengths, B: int, Ln: int, device) -> Optional[torch.Tensor]:
@@ -184,7 +182,7 @@ def _lengths(lengths, B: int, Ln: int, device) -> Optional[torch.Tensor]:
         host = np.asarray(lengths.numpy() if isinstance(lengths, torch.Tensor) else lengths).reshape(-1)
         if host.size and (host.min() < 1 or host.max() > Ln):
             raise ValueError(f"hvit metrics: lengths must lie in [1, {Ln}], got min {host.min()} max {host.max()}")
-    return FE._lengths_arg(lengths, B, device)
+    return lengths_arg(lengths, B, device, "hvit metrics")
 
 
 def wave_metrics(clean: torch.Tensor, est: torch.Tensor, lengths=None, frame_length: int = 512,
@@ -193,23 +191,18 @@ def wave_metrics(clean: torch.Tensor, est: torch.Tensor, lengths=None, frame_len
     (float32 GPU ``[B, L]``; row b is ``[b, :lengths[b]]``) as float64 ``[B, 3]``,
     with compute_sisdr / compute_snr / compute_segsnr's definitions.
     ``frame_length`` must be a multiple of ``hop_length``, at most 16 times it."""
-    clean, est = _wave_arg(clean, "clean"), _wave_arg(est, "est")
-    if clean.shape != est.shape or clean.device != est.device:
-        raise ValueError(f"hvit metrics: clean {tuple(clean.shape)} on {clean.device} and est {tuple(est.shape)} on "
-                         f"{est.device} must match")
+    clean, est, B, Ln, cs, es = _pair_arg(clean, est)
     if hop_length < 1 or frame_length < hop_length or frame_length % hop_length or frame_length > 16 * hop_length:
         raise ValueError(f"hvit metrics: frame_length={frame_length} must be a positive multiple of "
                          f"hop_length={hop_length}, at most 16 times it")
-    B, Ln = clean.shape
     dev = clean.device
     lens = _lengths(lengths, B, Ln, dev)
     n_ws = L.lib().hvit_wave_metrics_ws_elems(B, Ln, hop_length)
     ws = torch.empty(n_ws, dtype=torch.float64, device=dev)
     out = torch.empty((B, 3), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        L.call("hvit_wave_metrics", clean.data_ptr(), clean.stride(0) if B > 1 else Ln, est.data_ptr(),
-               est.stride(0) if B > 1 else Ln, L.ptr(lens), B, Ln, frame_length, hop_length, float(eps),
-               ws.data_ptr(), n_ws, out.data_ptr(), L.stream_ptr(dev))
+        L.call("hvit_wave_metrics", clean.data_ptr(), cs, est.data_ptr(), es, L.ptr(lens), B, Ln, frame_length,
+               hop_length, float(eps), ws.data_ptr(), n_ws, out.data_ptr(), L.stream_ptr(dev))
     return out
 
 
@@ -217,11 +210,7 @@ def lsd(clean: torch.Tensor, est: torch.Tensor, lengths=None, n_fft: int = 512, 
         eps: float = 1e-10) -> torch.Tensor:
     """Log-spectral distance of every row (compute_lsd's definition on the
     device front end's magnitudes) as float64 ``[B]``."""
-    clean, est = _wave_arg(clean, "clean"), _wave_arg(est, "est")
-    if clean.shape != est.shape or clean.device != est.device:
-        raise ValueError(f"hvit metrics: clean {tuple(clean.shape)} on {clean.device} and est {tuple(est.shape)} on "
-                         f"{est.device} must match")
-    B, Ln = clean.shape
+    clean, est, B, Ln, _, _ = _pair_arg(clean, est)
     dev = clean.device
     lens = _lengths(lengths, B, Ln, dev)
     mag_c = FE.stft_mag(clean, lens, n_fft, hop_length, n_fft)
@@ -253,13 +242,13 @@ def all_metrics_batch(clean: torch.Tensor, enhanced: torch.Tensor, noisy: Option
     noisy rows are scored against clean in one ``wave_metrics`` call of 2 B
     rows.  PESQ and STOI are host libraries: they are zeros unless the package
     can be imported, in which case the rows are downloaded for them."""
-    clean, enhanced = _wave_arg(clean, "clean"), _wave_arg(enhanced, "enhanced")
-    B, Ln = clean.shape
+    clean, B, Ln, _ = wave_arg(clean, "hvit metrics", "clean")
+    enhanced = wave_arg(enhanced, "hvit metrics", "enhanced")[0]
     lens = _lengths(lengths, B, Ln, clean.device)
     if noisy is None:
         wm = wave_metrics(clean, enhanced, lens)
     else:
-        noisy = _wave_arg(noisy, "noisy")
+        noisy = wave_arg(noisy, "hvit metrics", "noisy")[0]
         both = wave_metrics(torch.cat([clean, clean]), torch.cat([enhanced, noisy]),
                             None if lens is None else torch.cat([lens, lens]))
         wm, wm_noisy = both[:B], both[B:]

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._args import canonical_device, lengths_arg, wave_arg
 
 TILE = 256  # outputs per workgroup (csrc/wave_resample.hip: WR_TILE)
 ZEROS, ROLLOFF, BETA = 64, 0.9475937167399596, 14.769656459379492
@@ -135,9 +136,7 @@ def taps_table(orig_sr: int, target_sr: int, device, zeros: int = ZEROS, rolloff
     """``(taps_pp f32 device [up, J], up, down, half)``: the design rounded
     once from float64, in phase-major layout; cached per device, ratio and
     design."""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = canonical_device(device)
     up, down = ratio(orig_sr, target_sr)
     key = (str(device), up, down, int(zeros), float(rolloff), float(beta))
     hit = _tables.get(key)
@@ -161,13 +160,8 @@ def resample_wave(wave: torch.Tensor, lengths, orig_sr: int, target_sr: int, ret
     read back) or an int32 device tensor (``L_out`` is then sized for L).
     ``out_len`` fixes ``L_out``; outputs past it are dropped.  Equal rates return
     ``wave`` itself without a launch."""
-    if not isinstance(wave, torch.Tensor):
-        raise TypeError("hvit resampler: wave must be a torch.Tensor")
-    if not wave.is_cuda:
-        raise RuntimeError("hvit resampler: wave must be a GPU tensor; there is no CPU path")
-    if wave.dim() != 2 or wave.dtype != torch.float32 or wave.shape[1] < 1 or wave.shape[0] < 1:
-        raise ValueError(f"hvit resampler: wave must be float32 [B, L], got {wave.dtype} {tuple(wave.shape)}")
-    B, Ln = wave.shape
+    given = wave
+    wave, B, Ln, row_stride = wave_arg(wave, "hvit resampler", "wave")
     dev = wave.device
     up, down = ratio(orig_sr, target_sr)
     host_lens = None
@@ -175,33 +169,21 @@ def resample_wave(wave: torch.Tensor, lengths, orig_sr: int, target_sr: int, ret
         host_lens = np.asarray(lengths, dtype=np.int64).reshape(-1)
         if host_lens.shape != (B,) or (host_lens < 0).any() or (host_lens > Ln).any():
             raise ValueError(f"hvit resampler: lengths must be {B} values in [0, {Ln}]")
-    elif lengths is not None and tuple(lengths.shape) != (B,):
-        raise ValueError(f"hvit resampler: lengths must have shape ({B},), got {tuple(lengths.shape)}")
+    lens = lengths_arg(lengths if host_lens is None else host_lens, B, dev, "hvit resampler")
 
     if up == down:
-        if host_lens is not None:
-            ol = torch.from_numpy(host_lens.astype(np.int32)).to(dev)
-        elif lengths is not None:
-            ol = lengths.to(device=dev, dtype=torch.int32)
-        else:
-            ol = torch.full((B,), Ln, dtype=torch.int32, device=dev)
-        return (wave, ol, wave.abs().amax(1)) if return_peak else (wave, ol)
+        ol = lens if lens is not None else torch.full((B,), Ln, dtype=torch.int32, device=dev)
+        return (given, ol, given.abs().amax(1)) if return_peak else (given, ol)
 
-    if wave.stride(1) != 1 or (B > 1 and wave.stride(0) < Ln):
-        wave = wave.contiguous()
-    row_stride = wave.stride(0) if B > 1 else Ln  # a single row's stride is arbitrary (0 for a broadcast view)
     if host_lens is not None:
         olens = -(-host_lens * up // down)
         L_out = int(out_len) if out_len is not None else max(1, int(olens.max()))
-        lens = torch.from_numpy(host_lens.astype(np.int32)).to(dev)
         out_lengths = torch.from_numpy(np.minimum(olens, L_out).astype(np.int32)).to(dev)
     else:
         L_out = int(out_len) if out_len is not None else out_length(Ln, up, down)
-        if lengths is None:
-            lens = None
+        if lens is None:
             out_lengths = torch.full((B,), min(out_length(Ln, up, down), L_out), dtype=torch.int32, device=dev)
         else:
-            lens = lengths.to(device=dev, dtype=torch.int32).contiguous()
             ol = (lens.clamp(0, Ln).to(torch.int64) * up + (down - 1)) // down
             out_lengths = ol.clamp(max=L_out).to(torch.int32)
     if L_out < 1:
