@@ -12,12 +12,14 @@ The reference's flags (evaluate.py:27-73) with its meaning: the test pairs are
 with a warning (:79-83); the scores go to ``evaluation_results.json`` under
 ``--output-dir`` and, with ``--save-enhanced``, the enhanced clips to its
 ``enhanced`` folder.  Additions: ``--config`` (one more YAML merged on top),
-``--precision``, ``--frontend``, ``--batch-size`` and ``--resample`` (files at
+``--precision``, ``--frontend``, ``--batch-size``, ``--resample`` (files at
 another rate than the configured one are resampled to it on the GPU instead of
-refused; the scores are always computed at the configured rate).  With ``--frontend
+refused; the scores are always computed at the configured rate) and ``--stoi``
+(``native``: STOI by the project's own implementation, csrc/stoi.hip on the
+device front end, instead of the ``pystoi`` package).  With ``--frontend
 device`` the clips are enhanced and scored on the GPU in batches of
-``--batch-size`` (SI-SDR, SNR, SegSNR, LSD: csrc/metrics.hip); PESQ and STOI
-need the ``pesq`` / ``pystoi`` packages and read 0.0 without them.
+``--batch-size`` (SI-SDR, SNR, SegSNR, LSD: csrc/metrics.hip); PESQ and, by
+default, STOI need the ``pesq`` / ``pystoi`` packages and read 0.0 without them.
 """
 
 import argparse
@@ -46,6 +48,8 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=32, help="pairs per device batch (--frontend device)")
     ap.add_argument("--resample", action="store_true",
                     help="take files at any sample rate: resample them to the configured rate on the GPU")
+    ap.add_argument("--stoi", default="package", choices=["package", "native"],
+                    help="STOI from the pystoi package (0.0 without it) or the native implementation")
     a = ap.parse_args(argv)
     if a.batch_size < 1:
         ap.error(f"--batch-size must be at least 1, got {a.batch_size}")
@@ -66,7 +70,7 @@ def main(argv=None):
     print(f"Loading checkpoint from {a.checkpoint}")
     model = E.load_model_for_inference(a.checkpoint, model, a.device)
     evaluator = hv.Evaluator(model, device=a.device, frontend=a.frontend, batch_size=a.batch_size,
-                             resample=a.resample, **hv.audio_settings(cfg))
+                             resample=a.resample, stoi=a.stoi, **hv.audio_settings(cfg))
     print(f"Noisy directory: {noisy_dir}\nClean directory: {clean_dir}")
     enhanced_dir = output_dir / "enhanced" if a.save_enhanced else None
     results = evaluator.evaluate_dataset(noisy_dir, clean_dir, output_dir=enhanced_dir, save_enhanced=a.save_enhanced)

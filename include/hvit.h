@@ -600,6 +600,12 @@ long long hvit_wave_resample_out_len(long long len, int up, int down);
 int hvit_wave_resample(const float* wave, long long wave_stride, const int* lengths, int B, int L, int up, int down,
                        const float* taps_pp, int half, float* out, long long out_stride, int L_out, float* peak,
                        void* stream);
+/* The same with an f64 accumulator: every f32 x f32 product is exact, the sum
+ * of an output's terms is formed in f64 in the same order and rounded to f32
+ * once (for a caller that measures in f64 downstream: native STOI). */
+int hvit_wave_resample_f64acc(const float* wave, long long wave_stride, const int* lengths, int B, int L, int up,
+                              int down, const float* taps_pp, int half, float* out, long long out_stride, int L_out,
+                              float* peak, void* stream);
 
 /* Speech quality metrics on device waveforms and magnitudes (evaluation/metrics.py:
  * compute_sisdr :100-145, compute_snr :148-184, compute_segsnr :187-243,
@@ -633,6 +639,37 @@ int hvit_wave_metrics(const float* clean, long long clean_stride, const float* e
 long long hvit_lsd_ws_elems(int B, int T);
 int hvit_lsd(const float* mag_a, const float* mag_b, const int* lengths, int B, int F, int T, int hop, double eps,
              double* ws, long long ws_elems, double* out, void* stream);
+
+/* Short-time objective intelligibility (Taal et al. 2011, non-extended, with
+ * pystoi's constants) of rows that are already at 10 kHz.  With w =
+ * hanning(258)[1:-1] and EPS = 2^-52:
+ *   frames   frame j = w * x[128 j : 128 j + 256] for every j with 128 j + 256 <=
+ *            len_b (every full frame, the last included);
+ *   silence  on clean alone, e_j = 20 log10(|frame_j| + EPS); frame j is kept when
+ *            e_j > max_j e - 40; the K kept frames of clean and of est are
+ *            overlap-added at hop 128 in their compacted order ((K + 1) * 128 samples);
+ *   bands    the rebuilt signals are framed again (K frames), transformed at 512
+ *            points, and tob[band, m] = sqrt(sum of |X[k, m]|^2) over the 15
+ *            third-octave bin ranges [7,9) [9,11) [11,14) [14,17) [17,22) [22,27)
+ *            [27,34) [34,43) [43,55) [55,69) [69,87) [87,109) [109,138) [138,174) [174,219);
+ *   score    K < 30: 1e-5 exactly.  Otherwise, for each of the K - 29 runs of 30
+ *            frames and each band, with x / y the clean / est values: y' = min(y |x| /
+ *            (|y| + EPS), (1 + 10^(15/20)) x); both lose their mean and are divided
+ *            by their norm plus EPS; out[b] is the sum of their products over
+ *            15 (K - 29).
+ * clean, est [B, L] f32 (row strides in elements), lengths as for
+ * hvit_wave_metrics except that len_b = 0 is allowed (nullable; nothing at or
+ * past len_b is loaded), out [B] f64; ws is caller scratch of at least
+ * hvit_stoi_ws_elems(B, L) doubles, 8-byte aligned.  Every product, transform,
+ * sum, log and square root is f64; the window and the twiddles are computed in
+ * f64 on the device into ws, once per call.  K is known on the device only: the
+ * workspace and the grids are sized for "every frame kept".  The call neither
+ * allocates nor synchronises (it can be captured in a hipGraph).  No float
+ * atomics: a row's result is bit-identical from run to run and does not depend
+ * on the rest of the batch, on L or on the strides. */
+long long hvit_stoi_ws_elems(int B, int L);
+int hvit_stoi(const float* clean, long long clean_stride, const float* est, long long est_stride, const int* lengths,
+              int B, int L, double* ws, long long ws_elems, double* out, void* stream);
 
 /* Training batches assembled on the device: the reference's cached
  * __getitem__ (data/dataset.py:233-294), SpectrogramAugmenter.augment on the

@@ -13,6 +13,7 @@ plus the factory it forgot to export):
     compute_sisdr / compute_snr / compute_segsnr / compute_lsd / compute_pesq / compute_stoi /
     compute_all_metrics / print_metrics (evaluation/metrics.py on the host), wave_metrics / lsd /
     all_metrics_batch (the same scores on GPU batches, metrics.py) and Evaluator (evaluation/evaluator.py),
+    stoi / stoi_reference / stoi_taps / third_octave_bands (native STOI on the device and its float64 host reference),
     SpectrogramAugmenter / plan_host / apply_plan_host (data/augmentation.py drawn on the device, augment.py),
     SpectrogramStore / DeviceBatchLoader (the dataset cached on the GPU and its loader, data.py),
     create_scheduler / WarmupCosineScheduler (training/optimizer.py:76-200) and Trainer (training/trainer.py)
@@ -54,6 +55,10 @@ from .metrics import (  # noqa: F401
     compute_stoi,
     lsd,
     print_metrics,
+    stoi,
+    stoi_reference,
+    stoi_taps,
+    third_octave_bands,
     wave_metrics,
 )
 from .evaluator import Evaluator  # noqa: F401
@@ -69,7 +74,8 @@ __all__ = [
     "load_all_configs", "load_config", "merge_configs", "load_cli_configs", "audio_settings", "stft_mag", "istft_mag",
     "supported", "n_frames",
     "resample_wave", "resample_taps", "resample_reference", "compute_sisdr", "compute_snr", "compute_segsnr", "compute_lsd", "compute_pesq", "compute_stoi",
-    "compute_all_metrics", "print_metrics", "wave_metrics", "lsd", "all_metrics_batch", "Evaluator",
+    "compute_all_metrics", "print_metrics", "wave_metrics", "lsd", "all_metrics_batch", "stoi", "stoi_reference",
+    "stoi_taps", "third_octave_bands", "Evaluator",
     "SpectrogramAugmenter", "plan_host", "apply_plan_host", "SpectrogramStore", "DeviceBatchLoader",
     "create_scheduler", "WarmupCosineScheduler", "Trainer",
 ]

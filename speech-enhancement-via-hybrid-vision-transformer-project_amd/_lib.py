@@ -184,10 +184,13 @@ _SIGS = {
     "hvit_istft": ([vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp], i32),
     "hvit_wave_resample_out_len": ([i64, i32, i32], i64),
     "hvit_wave_resample": ([vp, i64, vp, i32, i32, i32, i32, vp, i32, vp, i64, i32, vp, vp], i32),
-    "hvit_wave_metrics_ws_elems": ([i32, i32, i32], i64),
+    "hvit_wave_resample_f64acc": ([vp, i64, vp, i32, i32, i32, i32, vp, i32, vp, i64, i32, vp, vp], i32),
+    "hvit_wave_metrics_ws_elems":([i32, i32, i32], i64),
     "hvit_wave_metrics": ([vp, i64, vp, i64, vp, i32, i32, i32, i32, f64, vp, i64, vp, vp], i32),
     "hvit_lsd_ws_elems": ([i32, i32], i64),
     "hvit_lsd": ([vp, vp, vp, i32, i32, i32, i32, f64, vp, i64, vp, vp], i32),
+    "hvit_stoi_ws_elems": ([i32, i32], i64),
+    "hvit_stoi": ([vp, i64, vp, i64, vp, i32, i32, vp, i64, vp, vp], i32),
     "hvit_batch_prep": ([vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, P(AugmentCfg), vp, vp, vp, vp, vp], i32),
 }
 

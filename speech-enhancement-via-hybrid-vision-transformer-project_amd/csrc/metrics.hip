@@ -23,7 +23,7 @@
 //    ascending order), then the same fixed-order mean over the frames.
 // No float atomics anywhere: results are bit-identical from run to run and do
 // not depend on which other rows share the batch.
-#include "common.h"
+#include "wave_f64.h"
 
 namespace hvit {
 
@@ -37,27 +37,6 @@ constexpr int WM_PART = WM_MOM + 2;  // doubles per chunk: the moments, then the
 constexpr int WM_MAX_RATIO = 16;     // largest seg_frame / seg_hop
 constexpr int LSD_FRAMES = 16;  // frames per workgroup
 constexpr int LSD_SLICES = 16;  // bin slices per workgroup
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Sum of one value per thread of a 256-thread workgroup, in every thread:
-// butterfly per wave, then the four wave sums in ascending order.  One call
-// per kernel: nothing guards red against a second use.
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-  v = wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-__device__ __forceinline__ int row_len(const int* lengths, int b, int L) {
-  const int len = lengths ? lengths[b] : L;
-  return len < 0 ? 0 : (len > L ? L : len);
-}
 
 // LDS: the block sums {sum c^2, sum d^2} of the chunk's own blocks and of the WM_MAX_RATIO - 1 that follow
 __global__ __launch_bounds__(WM_THREADS) void wave_chunks_kernel(const float* __restrict__ clean, long clean_stride,

@@ -20,6 +20,10 @@
 // peak[b] = max |out[b, :]|: a maximum is exact in any order, so one integer
 // atomicMax per workgroup on the bit image of the non-negative float keeps it
 // deterministic (no float atomics).
+//
+// The accumulator is f32 (hvit_wave_resample) or f64 (hvit_wave_resample_f64acc:
+// every f32 x f32 product is exact in f64 and the sum is rounded to f32 once,
+// for callers that measure in f64 downstream, native STOI).
 #include "common.h"
 
 namespace hvit {
@@ -33,7 +37,11 @@ __global__ void wave_resample_peak_init_kernel(unsigned* peak, int B) {
   if (i < B) peak[i] = 0u;
 }
 
+__device__ __forceinline__ float wr_fma(float a, float b, float c) { return fmaf(a, b, c); }
+__device__ __forceinline__ double wr_fma(float a, float b, double c) { return fma((double)a, (double)b, c); }
+
 // LDS: span [<= (WR_TILE - 1) * down / up + 1 + J] float
+template <typename Acc>
 __global__ __launch_bounds__(WR_THREADS) void wave_resample_kernel(const float* __restrict__ wave, long wave_stride,
                                                                    const int* __restrict__ lengths, int L, int up,
                                                                    int down, const float* __restrict__ taps_pp,
@@ -66,7 +74,7 @@ __global__ __launch_bounds__(WR_THREADS) void wave_resample_kernel(const float* 
   }
   __syncthreads();
 
-  float acc = 0.f;
+  float res = 0.f;
   if (m < Lo) {
     const long pos = (long)half + (long)m * down;
     const long q = pos / up;
@@ -77,14 +85,16 @@ __global__ __launch_bounds__(WR_THREADS) void wave_resample_kernel(const float* 
     const int jlo = jl > 0 ? (int)jl : 0;
     const float* h = taps_pp + (size_t)p * J;
     const float* x = span + (q - kb);
-    for (int j = jlo; j <= jhi; ++j) acc = fmaf(h[j], x[-j], acc);
-    orow[m] = acc;
+    Acc acc = 0;
+    for (int j = jlo; j <= jhi; ++j) acc = wr_fma(h[j], x[-j], acc);
+    res = (float)acc;
+    orow[m] = res;
   } else if (m < L_out) {
     orow[m] = 0.f;
   }
 
   if (peak) {
-    const float v = wave_max(fabsf(acc));
+    const float v = wave_max(fabsf(res));
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     if (tid == 0) {
@@ -114,9 +124,10 @@ long long hvit_wave_resample_out_len(long long len, int up, int down) {
   return (len * up + down - 1) / down;
 }
 
-int hvit_wave_resample(const float* wave, long long wave_stride, const int* lengths, int B, int L, int up, int down,
-                       const float* taps_pp, int half, float* out, long long out_stride, int L_out, float* peak,
-                       void* stream) {
+template <typename Acc>
+static int wave_resample(const float* wave, long long wave_stride, const int* lengths, int B, int L, int up, int down,
+                         const float* taps_pp, int half, float* out, long long out_stride, int L_out, float* peak,
+                         void* stream) {
   HVIT_CHECK(wave && taps_pp && out, "hvit_wave_resample: null pointer");
   HVIT_CHECK(B >= 1 && B <= 65535 && L >= 1 && wave_stride >= L, "hvit_wave_resample: B=%d L=%d stride=%lld", B, L,
              wave_stride);
@@ -137,11 +148,25 @@ int hvit_wave_resample(const float* wave, long long wave_stride, const int* leng
     HVIT_LAUNCH_CHECK();
   }
   if (smem > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)wave_resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)wave_resample_kernel<Acc>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)smem);
-  hipLaunchKernelGGL(wave_resample_kernel, dim3(cdiv(L_out, WR_TILE), B), dim3(WR_THREADS), smem, st, wave,
+  hipLaunchKernelGGL(wave_resample_kernel<Acc>, dim3(cdiv(L_out, WR_TILE), B), dim3(WR_THREADS), smem, st, wave,
                      (long)wave_stride, lengths, L, up, down, taps_pp, half, J, out, (long)out_stride, L_out,
                      (unsigned*)peak);
   HVIT_LAUNCH_CHECK();
   return HVIT_OK;
+}
+
+int hvit_wave_resample(const float* wave, long long wave_stride, const int* lengths, int B, int L, int up, int down,
+                       const float* taps_pp, int half, float* out, long long out_stride, int L_out, float* peak,
+                       void* stream) {
+  return wave_resample<float>(wave, wave_stride, lengths, B, L, up, down, taps_pp, half, out, out_stride, L_out, peak,
+                              stream);
+}
+
+int hvit_wave_resample_f64acc(const float* wave, long long wave_stride, const int* lengths, int B, int L, int up,
+                              int down, const float* taps_pp, int half, float* out, long long out_stride, int L_out,
+                              float* peak, void* stream) {
+  return wave_resample<double>(wave, wave_stride, lengths, B, L, up, down, taps_pp, half, out, out_stride, L_out,
+                               peak, stream);
 }

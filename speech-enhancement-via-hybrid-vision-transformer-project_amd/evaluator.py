@@ -36,11 +36,15 @@ class Evaluator:
     ``resample`` (True: a file at another rate is resampled to ``sample_rate``
     on the device as it is loaded, noisy and clean each at its own rate, as the
     reference's librosa.load(sr=16000) does; the metrics are always computed at
-    ``sample_rate``.  The default refuses such a file)."""
+    ``sample_rate``.  The default refuses such a file) and ``stoi`` ("package":
+    the ``pystoi`` package, 0.0 without it; "native": ``metrics.stoi`` on the
+    device front end, ``metrics.stoi_reference`` on the host one)."""
 
     def __init__(self, model: nn.Module, device: str = "cuda", sample_rate: int = SR, n_fft: int = N_FFT,
                  hop_length: int = HOP, win_length: int = WIN, frontend: str = "host", batch_size: int = 32,
-                 precision: Optional[str] = None, resample: bool = False):
+                 precision: Optional[str] = None, resample: bool = False, stoi: str = "package"):
+        if stoi not in ("package", "native"):
+            raise ValueError(f"hvit evaluator: stoi={stoi!r} ('package' or 'native')")
         if batch_size < 1:
             raise ValueError(f"hvit evaluator: batch_size={batch_size}")
         if precision is not None:
@@ -59,6 +63,7 @@ class Evaluator:
         self.frontend = frontend
         self.batch_size = int(batch_size)
         self.resample = bool(resample)
+        self.stoi = stoi
 
     def enhance_audio(self, noisy_audio: np.ndarray) -> np.ndarray:
         """evaluator.py:54-117."""
@@ -82,7 +87,7 @@ class Evaluator:
 
     def _score_host(self, noisy: np.ndarray, clean: np.ndarray):
         enhanced = self.enhance_audio(noisy)[:len(clean)]
-        return M.compute_all_metrics(clean, enhanced, noisy, self.sample_rate), enhanced
+        return M.compute_all_metrics(clean, enhanced, noisy, self.sample_rate, stoi=self.stoi), enhanced
 
     @torch.no_grad()
     def _score_device(self, noisy_clips, clean_clips):
@@ -92,7 +97,7 @@ class Evaluator:
         batch = WaveBatch.from_clips(noisy_clips, self.device, self.sample_rate, self.sample_rate, peak=True)
         enhanced = self.enhancer._enhance_device_tensor(batch, True)
         ref = upload_rows(clean_clips + noisy_clips, enhanced.device, width=enhanced.shape[1])
-        scores = M.all_metrics_batch(ref[:n], enhanced, ref[n:], batch.lengths)
+        scores = M.all_metrics_batch(ref[:n], enhanced, ref[n:], batch.lengths, stoi=self.stoi, sr=self.sample_rate)
         names = list(scores)
         table = torch.stack([scores[k] for k in names]).cpu().numpy()  # the batch's one download
         return [{k: float(table[j, r]) for j, k in enumerate(names)} for r in range(n)], enhanced

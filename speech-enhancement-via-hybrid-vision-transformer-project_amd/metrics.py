@@ -9,7 +9,10 @@ silent signal gives ``-inf`` as numpy's log10(0) does.  ``compute_lsd``
 center=True, zero padding: librosa is not installed here, where the reference
 itself returns 0.0).  ``compute_pesq`` / ``compute_stoi`` (:16-97) call the
 ``pesq`` / ``pystoi`` packages when they can be imported and otherwise return
-0.0 after one warning per process; there are no kernels for them.
+0.0 after one warning per process; there is no kernel for PESQ.  STOI also has
+a native form: ``stoi_reference`` is its definition in numpy
+float64 and ``stoi`` the same on GPU batches (csrc/stoi.hip behind hvit_stoi);
+``stoi="native"`` on ``compute_all_metrics`` / ``all_metrics_batch`` selects it.
 
 Device: ``wave_metrics`` gives {SI-SDR, SNR, SegSNR} per row of a ragged f32
 batch as float64 ``[B, 3]``; ``lsd`` is two ``stft_mag`` calls and hvit_lsd;
@@ -22,6 +25,7 @@ path behind them: a CPU tensor is an error.
 from __future__ import annotations
 
 import importlib
+import math
 import warnings
 from typing import Dict, Optional
 
@@ -30,6 +34,7 @@ import torch
 
 from . import _lib as L
 from . import frontend as FE
+from . import resampler as RS
 from ._args import lengths_arg, wave_arg
 
 _warned = set()
@@ -134,13 +139,125 @@ def compute_lsd(clean: np.ndarray, enhanced: np.ndarray, sr: int = 16000, n_fft:
     return float(np.mean(np.sqrt(np.mean(d ** 2, axis=0))))
 
 
+# ------------------------------------------------------------- native STOI --
+# Taal et al. 2011, non-extended, with the constants pystoi uses.
+STOI_FS, STOI_FRAME, STOI_HOP, STOI_NFFT, STOI_BANDS, STOI_MINF = 10000, 256, 128, 512, 15, 150.0
+STOI_SEG, STOI_BETA, STOI_DYN = 30, -15.0, 40.0
+STOI_SHORT = 1e-5  # the score of a clip with fewer than STOI_SEG frames left
+EPS = float(np.finfo(float).eps)
+
+
+def stoi_taps(sr: int):
+    """``(h float64 [2 * half + 1], up, down, half)``: the Kaiser-windowed sinc
+    STOI resamples ``sr`` -> 10 kHz with (60 dB stop band, transition a tenth of
+    the cut-off), before normalisation: ``resample_poly(x, up, down,
+    window=h / sum(h))`` is the resampled clip."""
+    g = math.gcd(STOI_FS, int(sr))
+    up, down = STOI_FS // g, int(sr) // g
+    fc = 1.0 / (2 * max(up, down))
+    half = int(math.ceil((60.0 - 8.0) / (28.714 * (fc / 10.0))))
+    t = np.arange(-half, half + 1, dtype=np.float64)
+    h = np.kaiser(2 * half + 1, 0.1102 * (60.0 - 8.7)) * (2 * up * fc) * np.sinc(2 * fc * t)
+    return h, up, down, half
+
+
+def third_octave_bands():
+    """The 15 half-open rfft bin ranges ``[(lo, hi), ...]`` at 10 kHz / 512: the
+    edges 150 * 2^((2 b -+ 1) / 6) Hz, each snapped to the nearest bin."""
+    f = np.linspace(0, STOI_FS, STOI_NFFT + 1)[:STOI_NFFT // 2 + 1]
+    k = np.arange(STOI_BANDS, dtype=np.float64)
+    lo = STOI_MINF * 2.0 ** ((2 * k - 1) / 6)
+    hi = STOI_MINF * 2.0 ** ((2 * k + 1) / 6)
+    return [(int(np.argmin((f - a) ** 2)), int(np.argmin((f - b) ** 2))) for a, b in zip(lo, hi)]
+
+
+def stoi_resample(x: np.ndarray, sr: int) -> np.ndarray:
+    """``x`` at 10 kHz in float64: ``x`` itself when ``sr`` is 10000."""
+    if int(sr) == STOI_FS:
+        return x
+    from scipy.signal import resample_poly
+
+    h, up, down, _ = stoi_taps(sr)
+    return resample_poly(np.asarray(x, dtype=np.float64), up, down, window=h / np.sum(h))
+
+
+def _stoi_frames(x: np.ndarray) -> np.ndarray:
+    """Every full frame of ``x`` under hanning(258)[1:-1]: ``[frames, 256]``."""
+    w = np.hanning(STOI_FRAME + 2)[1:-1]
+    n = (len(x) - STOI_FRAME) // STOI_HOP + 1 if len(x) >= STOI_FRAME else 0
+    idx = STOI_HOP * np.arange(n)[:, None] + np.arange(STOI_FRAME)[None, :]
+    return w * x[idx]
+
+
+def _stoi_rebuild(frames: np.ndarray) -> np.ndarray:
+    out = np.zeros((len(frames) + 1) * STOI_HOP)
+    for i, f in enumerate(frames):
+        out[i * STOI_HOP:i * STOI_HOP + STOI_FRAME] += f
+    return out
+
+
+def _stoi_tob(x: np.ndarray) -> np.ndarray:
+    """Third-octave band magnitudes ``[15, frames]`` of a rebuilt signal."""
+    spec = np.fft.rfft(_stoi_frames(x), STOI_NFFT, axis=1)
+    power = spec.real ** 2 + spec.imag ** 2
+    return np.sqrt(np.stack([power[:, lo:hi].sum(axis=1) for lo, hi in third_octave_bands()]))
+
+
+def stoi_reference(clean, est, sr: int = 16000, details: bool = False):
+    """STOI of ``est`` against ``clean`` in numpy float64: the
+    yardstick hvit_stoi is tested against.  Every full frame counts, the last
+    one included.  With ``details`` the result is ``(score, K, margin, cond)``:
+    the kept frames, the smallest distance in dB of a frame energy from the
+    silence threshold and the smallest ``|x - mean x| / |x|`` over segments and
+    bands (``inf`` where there is nothing to take the minimum of)."""
+    x, y = _pair(clean, est)
+    x, y = stoi_resample(x, sr), stoi_resample(y, sr)
+    xf, yf = _stoi_frames(x), _stoi_frames(y)
+    margin = cond = float("inf")
+    if len(xf):
+        e = 20.0 * np.log10(np.sqrt(np.sum(xf ** 2, axis=1)) + EPS)
+        thr = np.max(e) - STOI_DYN
+        keep = e > thr
+        margin = float(np.min(np.abs(e - thr)))
+        xf, yf = xf[keep], yf[keep]
+    K = len(xf)
+    if K < STOI_SEG:
+        return (STOI_SHORT, K, margin, cond) if details else STOI_SHORT
+    X, Y = _stoi_tob(_stoi_rebuild(xf)), _stoi_tob(_stoi_rebuild(yf))
+    seg = np.arange(K - STOI_SEG + 1)[:, None] + np.arange(STOI_SEG)[None, :]
+    xs, ys = X[:, seg], Y[:, seg]  # [15, segments, 30]
+    nx = np.sqrt(np.sum(xs ** 2, axis=2, keepdims=True))
+    ny = np.sqrt(np.sum(ys ** 2, axis=2, keepdims=True))
+    yp = np.minimum((nx / (ny + EPS)) * ys, xs * (1.0 + 10.0 ** (-STOI_BETA / 20.0)))
+    xm = xs - np.mean(xs, axis=2, keepdims=True)
+    ym = yp - np.mean(yp, axis=2, keepdims=True)
+    nxm = np.sqrt(np.sum(xm ** 2, axis=2, keepdims=True))
+    xn = xm / (nxm + EPS)
+    yn = ym / (np.sqrt(np.sum(ym ** 2, axis=2, keepdims=True)) + EPS)
+    score = float(np.sum(xn * yn) / (STOI_BANDS * (K - STOI_SEG + 1)))
+    if details:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = nxm / nx
+        if np.isfinite(r).any():
+            cond = float(np.nanmin(r))
+        return score, K, margin, cond
+    return score
+
+
+def _stoi_host(clean, est, sr: int, stoi: str) -> float:
+    if stoi not in ("package", "native"):
+        raise ValueError(f"hvit metrics: stoi={stoi!r} ('package' or 'native')")
+    return compute_stoi(clean, est, sr) if stoi == "package" else stoi_reference(clean, est, sr)
+
+
 def compute_all_metrics(clean: np.ndarray, enhanced: np.ndarray, noisy: Optional[np.ndarray] = None,
-                        sr: int = 16000) -> Dict[str, float]:
+                        sr: int = 16000, stoi: str = "package") -> Dict[str, float]:
     """The reference's dict (metrics.py:299-349): six scores of ``enhanced`` and,
-    with ``noisy``, four improvements over it."""
+    with ``noisy``, four improvements over it.  ``stoi="native"`` takes STOI
+    from ``stoi_reference`` instead of the ``pystoi`` package."""
     m = {
         "pesq": compute_pesq(clean, enhanced, sr),
-        "stoi": compute_stoi(clean, enhanced, sr),
+        "stoi": _stoi_host(clean, enhanced, sr, stoi),
         "sisdr": compute_sisdr(clean, enhanced),
         "snr": compute_snr(clean, enhanced),
         "segsnr": compute_segsnr(clean, enhanced),
@@ -148,7 +265,7 @@ def compute_all_metrics(clean: np.ndarray, enhanced: np.ndarray, noisy: Optional
     }
     if noisy is not None:
         m["pesq_improvement"] = m["pesq"] - compute_pesq(clean, noisy, sr)
-        m["stoi_improvement"] = m["stoi"] - compute_stoi(clean, noisy, sr)
+        m["stoi_improvement"] = m["stoi"] - _stoi_host(clean, noisy, sr, stoi)
         m["sisdr_improvement"] = m["sisdr"] - compute_sisdr(clean, noisy)
         m["snr_improvement"] = m["snr"] - compute_snr(clean, noisy)
     return m
@@ -225,6 +342,38 @@ def lsd(clean: torch.Tensor, est: torch.Tensor, lengths=None, n_fft: int = 512, 
     return out
 
 
+def _stoi_design(sr: int):
+    h, up, down, half = stoi_taps(sr)
+    return up * h / np.sum(h), up, down, half
+
+
+def stoi(clean: torch.Tensor, est: torch.Tensor, lengths=None, sr: int = 16000) -> torch.Tensor:
+    """STOI of every row of ``est`` against ``clean`` (``stoi_reference``'s
+    definition) as float64 ``[B]``.  At another rate than 10 kHz both batches
+    are first resampled in one call of 2 B rows with STOI's own filter
+    (``stoi_taps``, rounded once to float32; the resampler sums in float64 and
+    rounds each 10 kHz sample to float32 once: hvit_wave_resample_f64acc)."""
+    clean, est, B, Ln, cs, es = _pair_arg(clean, est)
+    dev = clean.device
+    lens = _lengths(lengths, B, Ln, dev)
+    if int(sr) != STOI_FS:
+        table = RS.custom_taps_table(f"stoi-{int(sr)}", lambda: _stoi_design(sr), dev)
+        both, out_lens = RS.resample_wave(torch.cat([clean, est]), None if lens is None else torch.cat([lens, lens]),
+                                          sr, STOI_FS, taps=table, acc64=True)
+        clean, est, lens, Ln = both[:B], both[B:], out_lens[:B], both.shape[1]
+        cs = es = Ln
+    n_ws = L.lib().hvit_stoi_ws_elems(B, Ln)
+    ws = torch.empty(n_ws, dtype=torch.float64, device=dev)
+    out = torch.empty(B, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        L.call("hvit_stoi", clean.data_ptr(), cs, est.data_ptr(), es, L.ptr(lens), B, Ln, ws.data_ptr(), n_ws,
+               out.data_ptr(), L.stream_ptr(dev))
+    return out
+
+
+_stoi_device = stoi  # all_metrics_batch has a keyword of the same name
+
+
 def _host_rows(package: str, attr: str, fn, clean, other, lens):
     """A host-only score (PESQ, STOI) per row; zeros without a download when its package is absent."""
     B, Ln = clean.shape
@@ -236,25 +385,34 @@ def _host_rows(package: str, attr: str, fn, clean, other, lens):
 
 
 def all_metrics_batch(clean: torch.Tensor, enhanced: torch.Tensor, noisy: Optional[torch.Tensor] = None,
-                      lengths=None) -> Dict[str, torch.Tensor]:
+                      lengths=None, stoi: str = "package", sr: int = 16000) -> Dict[str, torch.Tensor]:
     """compute_all_metrics for a ragged GPU batch: float64 ``[B]`` device
     tensors under the reference's keys.  With ``noisy`` the enhanced and the
     noisy rows are scored against clean in one ``wave_metrics`` call of 2 B
     rows.  PESQ and STOI are host libraries: they are zeros unless the package
-    can be imported, in which case the rows are downloaded for them."""
+    can be imported, in which case the rows are downloaded for them.
+    ``stoi="native"`` fills ``stoi`` (and ``stoi_improvement``) on the device
+    instead (``stoi`` at ``sr``, enhanced and noisy in one call of 2 B rows)."""
+    if stoi not in ("package", "native"):
+        raise ValueError(f"hvit metrics: stoi={stoi!r} ('package' or 'native')")
     clean, B, Ln, _ = wave_arg(clean, "hvit metrics", "clean")
     enhanced = wave_arg(enhanced, "hvit metrics", "enhanced")[0]
     lens = _lengths(lengths, B, Ln, clean.device)
     if noisy is None:
         wm = wave_metrics(clean, enhanced, lens)
+        st = _stoi_device(clean, enhanced, lens, sr) if stoi == "native" else None
     else:
         noisy = wave_arg(noisy, "hvit metrics", "noisy")[0]
-        both = wave_metrics(torch.cat([clean, clean]), torch.cat([enhanced, noisy]),
-                            None if lens is None else torch.cat([lens, lens]))
+        clean2, est2 = torch.cat([clean, clean]), torch.cat([enhanced, noisy])
+        lens2 = None if lens is None else torch.cat([lens, lens])
+        both = wave_metrics(clean2, est2, lens2)
         wm, wm_noisy = both[:B], both[B:]
+        if stoi == "native":
+            st2 = _stoi_device(clean2, est2, lens2, sr)
+            st, st_noisy = st2[:B].contiguous(), st2[B:]
     m = {
         "pesq": _host_rows("pesq", "pesq", compute_pesq, clean, enhanced, lens),
-        "stoi": _host_rows("pystoi", "stoi", compute_stoi, clean, enhanced, lens),
+        "stoi": st if stoi == "native" else _host_rows("pystoi", "stoi", compute_stoi, clean, enhanced, lens),
         "sisdr": wm[:, 0].contiguous(),
         "snr": wm[:, 1].contiguous(),
         "segsnr": wm[:, 2].contiguous(),
@@ -262,11 +420,13 @@ def all_metrics_batch(clean: torch.Tensor, enhanced: torch.Tensor, noisy: Option
     }
     if noisy is not None:
         m["pesq_improvement"] = m["pesq"] - _host_rows("pesq", "pesq", compute_pesq, clean, noisy, lens)
-        m["stoi_improvement"] = m["stoi"] - _host_rows("pystoi", "stoi", compute_stoi, clean, noisy, lens)
+        m["stoi_improvement"] = m["stoi"] - (st_noisy if stoi == "native" else
+                                             _host_rows("pystoi", "stoi", compute_stoi, clean, noisy, lens))
         m["sisdr_improvement"] = m["sisdr"] - wm_noisy[:, 0]
         m["snr_improvement"] = m["snr"] - wm_noisy[:, 1]
     return m
 
 
 __all__ = ["compute_pesq", "compute_stoi", "compute_sisdr", "compute_snr", "compute_segsnr", "compute_lsd",
-           "compute_all_metrics", "print_metrics", "wave_metrics", "lsd", "all_metrics_batch"]
+           "compute_all_metrics", "print_metrics", "wave_metrics", "lsd", "all_metrics_batch", "stoi_taps",
+           "third_octave_bands", "stoi_reference", "stoi"]

@@ -147,8 +147,26 @@ def taps_table(orig_sr: int, target_sr: int, device, zeros: int = ZEROS, rolloff
     return hit
 
 
+def custom_taps_table(name: str, design, device):
+    """``taps_table`` for a caller's filter: ``design()`` returns ``(h float64
+    [2 * half + 1] already times up, up, down, half)``; it is rounded once to
+    float32, laid out phase-major and cached per device and ``name`` (which
+    must identify the design: ``design`` runs only on a miss)."""
+    device = canonical_device(device)
+    key = (str(device), "custom", name)
+    hit = _tables.get(key)
+    if hit is None:
+        h, up, down, half = design()
+        h = np.asarray(h, dtype=np.float64).reshape(-1)
+        if h.shape[0] != 2 * half + 1 or math.gcd(up, down) != 1:
+            raise ValueError(f"hvit resampler: table {name!r} needs 2 * half + 1 taps and coprime up / down")
+        pp = torch.from_numpy(taps_phase_major(h.astype(np.float32), up)).to(device)
+        hit = _tables[key] = (pp, int(up), int(down), int(half))
+    return hit
+
+
 def resample_wave(wave: torch.Tensor, lengths, orig_sr: int, target_sr: int, return_peak: bool = False,
-                  out_len: Optional[int] = None):
+                  out_len: Optional[int] = None, taps=None, acc64: bool = False):
     """Resample a float32 GPU batch ``wave`` [B, L] (row b is ``wave[b,
     :lengths[b]]``; what the buffer holds past it is ignored) from ``orig_sr``
     to ``target_sr``: ``(out [B, L_out], out_lengths int32 [B])``, plus ``peak
@@ -159,7 +177,10 @@ def resample_wave(wave: torch.Tensor, lengths, orig_sr: int, target_sr: int, ret
     and ``L_out`` then come from the integer formula on the host: nothing is
     read back) or an int32 device tensor (``L_out`` is then sized for L).
     ``out_len`` fixes ``L_out``; outputs past it are dropped.  Equal rates return
-    ``wave`` itself without a launch."""
+    ``wave`` itself without a launch.  ``taps`` replaces the default design by a
+    table of ``taps_table``'s form for the same ratio (``custom_taps_table``);
+    ``acc64`` sums every output in float64 before its one rounding to float32
+    (hvit_wave_resample_f64acc) instead of in float32."""
     given = wave
     wave, B, Ln, row_stride = wave_arg(wave, "hvit resampler", "wave")
     dev = wave.device
@@ -188,14 +209,19 @@ def resample_wave(wave: torch.Tensor, lengths, orig_sr: int, target_sr: int, ret
             out_lengths = ol.clamp(max=L_out).to(torch.int32)
     if L_out < 1:
         raise ValueError(f"hvit resampler: output length {L_out}")
-    taps_pp, up, down, half = taps_table(orig_sr, target_sr, dev)
+    if taps is None:
+        taps = taps_table(orig_sr, target_sr, dev)
+    elif (taps[1], taps[2]) != (up, down) or taps[0].device != dev:
+        raise ValueError(f"hvit resampler: taps table for {taps[1]}/{taps[2]} on {taps[0].device}, "
+                         f"call is {up}/{down} on {dev}")
+    taps_pp, up, down, half = taps
     out = torch.empty((B, L_out), dtype=torch.float32, device=dev)
     peak = torch.empty(B, dtype=torch.float32, device=dev) if return_peak else None
     with torch.cuda.device(dev):
-        L.call("hvit_wave_resample", wave.data_ptr(), row_stride, L.ptr(lens), B, Ln, up, down, taps_pp.data_ptr(),
+        L.call("hvit_wave_resample_f64acc" if acc64 else "hvit_wave_resample", wave.data_ptr(), row_stride, L.ptr(lens), B, Ln, up, down, taps_pp.data_ptr(),
                half, out.data_ptr(), L_out, L_out, L.ptr(peak), L.stream_ptr(dev))
     return (out, out_lengths, peak) if return_peak else (out, out_lengths)
 
 
 __all__ = ["TILE", "ratio", "out_length", "resample_taps", "taps_phase_major", "taps_from_phase_major",
-           "resample_reference", "taps_table", "resample_wave"]
+           "resample_reference", "taps_table", "custom_taps_table", "resample_wave"]
