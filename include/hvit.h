@@ -84,7 +84,9 @@ typedef struct {
  *   v  = acc (+ bias[n]) (+ rowadd[(m % rowadd_rows) * N + n])
  *   GELU_DUAL: y = v (pre-activation); out2 = dropout(gelu(v))      -> stop
  *     (GELU_DUAL_D: y = gelu'(v) instead, the MUL_AUX operand of the backward;
- *      GELU_DUAL_DK: y = keep * scale * gelu'(v), the dropout mask folded in)
+ *      GELU_DUAL_DK: y = keep * scale * gelu'(v), the dropout mask folded in;
+ *      GELU: only out2's value, stored to y.  The family stops before resid
+ *      and colsum: colsum with any of these four acts is HVIT_ERR_ARG)
  *   TANH: v = tanh(v) ; v = dropout(v) ; GELU_BWD: v *= gelu'(aux[m, n])
  *     (MUL_AUX: v *= aux[m, n])
  *   resid: v = resid[m, n] + rowscale[m / rows_per_sample] * v     (f32)
@@ -189,6 +191,35 @@ int hvit_gemm_tune(int what, int value);
  * on an H x W map of C channels (csrc/gemm_conv_halo.h), or -1 where that form
  * does not apply to the geometry.  No GPU work. */
 int hvit_conv_halo_off(int H, int W, int C, int rows, int hy, int hx, int chunk);
+/* Diagnostics (tests): which GEMM kernel a linear entry point would launch for
+ * these arguments, answered by the entry point's own host code (the launch and
+ * this query call one decision function).  No GPU work, no side job.
+ *  entry HVIT_PLAN_LINEAR_FWD / _DGRAD: (dt, M, N, K, bias, out = y / dx,
+ *    out_dt, epi) as hvit_linear_fwd / hvit_linear_dgrad take them (bias: fwd
+ *    only); the epilogue's pointers must be the real ones, their alignment
+ *    decides between the vector and the predicated epilogue.  ws_elems unused.
+ *  entry HVIT_PLAN_LINEAR_WGRAD: (dt, M, N, K) of hvit_linear_wgrad, out = dw,
+ *    bias = db (nullable), ws_elems = the workspace the call will get.
+ *  The x / w / dy operands (and the workspace) count as 16-byte aligned; the
+ *  HVIT_TUNE_RING knob is honoured as a launch honours it.
+ * plan:
+ *  ring      0: csrc/gemm.h's gemm_kernel; 2 / 4 / 5: that LDS-ring configuration
+ *            (csrc/gemm_ring.h)
+ *  tile      output tile class in the launcher's own code: 64 (64x64), 12864
+ *            (128x64), 128 (128x128), 256 (ring 4's 256x256); 0: no GEMM tile
+ *            kernel runs (M = 0, or the tall-skinny weight-gradient kernel)
+ *  epi_kind  compile-time epilogue kind: 0 generic (every field honoured, ragged
+ *            tiles), 1 plain store, 2 split-K slab, 3 GELU_DUAL family, 4 residual,
+ *            5 GELU backward / MUL_AUX (3 - 5: full aligned tiles only), 6 col2im
+ *  staging   K-loop operand staging: 0 through registers, 1 / 2 / 3 LDS-DMA with
+ *            that many stage buffers (the ring kernels: 2)
+ *  splits    K slices launched (1: no split-K; 0 with tile 0) */
+enum { HVIT_PLAN_LINEAR_FWD = 0, HVIT_PLAN_LINEAR_DGRAD = 1, HVIT_PLAN_LINEAR_WGRAD = 2 };
+typedef struct {
+  int ring, tile, epi_kind, staging, splits;
+} hvit_gemm_plan_t;
+int hvit_gemm_plan(int entry, int dt, int M, int N, int K, const float* bias, const void* out, int out_dt,
+                   const hvit_epilogue_t* epi, long long ws_elems, hvit_gemm_plan_t* plan);
 /* dw[N,K] = dy^T x; db[N] = colsum(dy) (nullable; fused when db == dw + N*K) */
 int hvit_linear_wgrad(int dt, const void* dy, const void* x, int M, int N, int K, float* dw, float* db,
                       float* ws, long long ws_elems, void* stream);

@@ -58,6 +58,19 @@ class Epilogue(C.Structure):
     ]
 
 
+class GemmPlan(C.Structure):
+    """hvit_gemm_plan_t: the kernel a linear entry point would launch (include/hvit.h)."""
+    _fields_ = [("ring", i32), ("tile", i32), ("epi_kind", i32), ("staging", i32), ("splits", i32)]
+
+    def astuple(self):
+        return (self.ring, self.tile, self.epi_kind, self.staging)
+
+
+PLAN_LINEAR_FWD, PLAN_LINEAR_DGRAD, PLAN_LINEAR_WGRAD = 0, 1, 2
+# hvit_gemm_plan_t.epi_kind (csrc/gemm_epilogue.h EpiKind)
+EK_GEN, EK_STORE, EK_SLAB, EK_GELU_DUAL, EK_RESID, EK_GELU_BWD, EK_PATCH = range(7)
+
+
 class ConvGeom(C.Structure):
     _fields_ = [
         ("src1", vp), ("C1", i32), ("src2", vp), ("C2", i32),
@@ -178,6 +191,7 @@ _SIGS = {
     "hvit_rng_advance": ([vp, vp, vp], i32),
     "hvit_gemm_tune": ([i32, i32], i32),
     "hvit_conv_halo_off": ([i32, i32, i32, i32, i32, i32, i32], i32),
+    "hvit_gemm_plan": ([i32, i32, i32, i32, i32, vp, vp, i32, P(Epilogue), i64, P(GemmPlan)], i32),
     "hvit_step_bump": ([vp, i32, f32, vp], i32),
     "hvit_stft_fwd": ([vp, i64, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp], i32),
     "hvit_spec_normalize": ([vp, i32, i32, i32, vp, i32, vp, i32, vp], i32),

@@ -1326,15 +1326,17 @@ struct IsDenseKC<LdDense<T, true>> : std::true_type {};
 
 // Effective split-K count after rounding each split to whole K-tiles (never
 // more than requested).  Callers that reduce slabs must use this count.
-template <typename T>
-inline int plan_splits(int K, int splits, int* kps_out = nullptr) {
-  constexpr int BK = KSTAGE / sizeof(T);
+inline int plan_splits_bk(int BK, int K, int splits, int* kps_out = nullptr) {
   if (splits < 1) splits = 1;
   int kps = (K + splits - 1) / splits;
   kps = ((kps + BK - 1) / BK) * BK;
   if (kps < BK) kps = BK;
   if (kps_out) *kps_out = kps;
   return K > 0 ? (K + kps - 1) / kps : 1;
+}
+template <typename T>
+inline int plan_splits(int K, int splits, int* kps_out = nullptr) {
+  return plan_splits_bk(KSTAGE / sizeof(T), K, splits, kps_out);
 }
 
 // tile: 128x128 when the grid still fills the chip; 128x64 for narrow
@@ -1353,20 +1355,83 @@ inline int auto_tile(int M, int N, int splits) {
   return 64;
 }
 
+// Which kernel a GEMM call launches: the whole choice, made from the shape, the
+// operands' traits and the epilogue alone.  gemm_plan (gemm.h's gemm_kernel) and
+// ring_plan (gemm_ring.h) are the only places that decide; launch_gemm / try_ring
+// dispatch on the result, and hvit_gemm_plan reports it without launching.
+struct GemmPlan {
+  int ring = 0;     // ring configuration (gemm_ring.h: 2 / 4 / 5), 0: gemm_kernel
+  int tile = 0;     // auto_tile's code (64, 12864, 128; ring 4: 256); 0: nothing to launch
+  int ek = EK_GEN;  // EpiKind
+  int stage = 0;    // K-loop staging: 0 registers, 1 / 2 / 3 LDS-DMA stage buffers (the rings: 2)
+  int splits = 1;   // K slices after rounding to whole stages
+  int kps = 0;      // K per slice
+};
+// what the choice needs to know of a loader pair
+struct GemmOperands {
+  int esize = 2;            // sizeof(T)
+  bool a_kc = true;         // LA::KC / LB::KC
+  bool b_kc = true;
+  bool a_dense_kc = false;  // A is LdDense<T, true> (the compile-time ViT kinds and the lean col2im exist)
+  bool dma_ok = false;      // an LDS-DMA K loop exists for the pair
+  bool conv_a = false;      // A is the bf16 implicit-im2col loader LdConvF
+  bool a_vok = true;        // dense operands: 16-byte aligned base, ld a multiple of 16 bytes
+  bool b_vok = true;
+  long a_bytes = 0;         // dense operands: byte extent (0 otherwise)
+  long b_bytes = 0;
+};
+template <class L>
+inline bool dense_vok(const L&) { return true; }
+template <typename T, bool KC>
+inline bool dense_vok(const LdDense<T, KC>& l) { return l.vok; }
+// compile-time traits of a loader pair: gemm_operands hands them to gemm_plan, launch_gemm
+// instantiates kernels by the same constants
 template <typename T, class LA, class LB>
-int launch_gemm(LA la, LB lb, int M, int N, int K, int splits, const Epi& ep_in, hipStream_t st,
-                int force_tile = 0) {
-  Epi ep = ep_in;
+struct GemmPair {
+  static constexpr bool CONV_A = IsConvFBf16<LA>::value;
+  // A-row sums (bias grad) only exist for the bf16 k-major A operand (wgrad)
+  static constexpr bool RS_OK = !LA::KC && sizeof(T) == 2;
+  // LDS-DMA K loops: dense bf16 operands (or the conv A loader).  Not with both operands
+  // k-major (the weight gradients): the register path measured faster there (0.82 vs 1.04
+  // ms/step)
+  static constexpr bool DMA_OK =
+      sizeof(T) == 2 && (IsDenseBf16<LA>::value || CONV_A) && IsDenseBf16<LB>::value && (LA::KC || LB::KC);
+};
+template <typename T, class LA, class LB>
+inline GemmOperands gemm_operands(const LA& la, const LB& lb) {
+  GemmOperands o;
+  o.esize = (int)sizeof(T);
+  o.a_kc = LA::KC;
+  o.b_kc = LB::KC;
+  o.a_dense_kc = IsDenseKC<LA>::value;
+  o.conv_a = GemmPair<T, LA, LB>::CONV_A;
+  o.dma_ok = GemmPair<T, LA, LB>::DMA_OK;
+  o.a_vok = dense_vok(la);
+  o.b_vok = dense_vok(lb);
+  o.a_bytes = dense_bytes(la);
+  o.b_bytes = dense_bytes(lb);
+  return o;
+}
+
+// both outputs of a GELU_DUAL epilogue are bf16 (out is absent in the GELU-only form)
+inline bool gelu_dual_bf16(const Epi& ep) {
+  return (!ep.out || ep.out_dt == HVIT_BF16) && ep.out2_dt == HVIT_BF16;
+}
+
+// Completes ep (slab stride, block order, vec_ok, dma) and fills p.  p.tile == 0:
+// an empty problem, nothing to launch.
+inline int gemm_plan(const GemmOperands& o, int M, int N, int K, int splits, int force_tile, Epi& ep, GemmPlan& p) {
+  p = GemmPlan();
   if (ep.slab_stride == 0) ep.slab_stride = (long)M * ep.ldo;
   ep.xcd_remap = 1;
   // the DMA loop addresses operands with 32-bit byte offsets
-  ep.dma = dense_bytes(la) < (1L << 31) && dense_bytes(lb) < (1L << 31);
+  ep.dma = o.a_bytes < (1L << 31) && o.b_bytes < (1L << 31);
   auto vok = [](const void* p, long ld) { return !p || ((((uintptr_t)p) & 15) == 0 && ld % 4 == 0); };
   ep.vec_ok = N % 4 == 0 && vok(ep.out, ep.ldo) && vok(ep.out2, ep.ldo2) && vok(ep.aux, ep.ldaux) &&
               vok(ep.resid, ep.ldr) && vok(ep.rowadd, ep.rowadd_ld);
   if (M <= 0 || N <= 0) return HVIT_OK;
   int kps = 0;
-  splits = plan_splits<T>(K, splits, &kps);
+  splits = plan_splits_bk(KSTAGE / o.esize, K, splits, &kps);
   if (splits > 1 && ep.mode != EPI_SLAB) {
     hvit_set_error("launch_gemm: split-K requires EPI_SLAB");
     return HVIT_ERR_ARG;
@@ -1384,16 +1449,16 @@ int launch_gemm(LA la, LB lb, int M, int N, int K, int splits, const Epi& ep_in,
     const bool patch_lean = ep.mode == EPI_PATCH && ep.pC % 4 == 0 && M % bm == 0 && N % bn == 0 && !ep.bias &&
                             ep.act == ACT_NONE && !ep.drop_thr && ep.drop_scale == 1.f && !ep.resid && !ep.rowadd &&
                             !ep.stats && !ep.colsum && ((uintptr_t)ep.out & 15) == 0;
-    if (IsDenseKC<LA>::value && ek == EK_GEN && patch_lean) ek = EK_PATCH;
-    if (IsDenseKC<LA>::value && ek == EK_GEN && full_tiles && drop_ok) {
+    if (o.a_dense_kc && ek == EK_GEN && patch_lean) ek = EK_PATCH;
+    if (o.a_dense_kc && ek == EK_GEN && full_tiles && drop_ok) {
       if (ep.act == ACT_GELU_DUAL && !ep.resid) ek = EK_GELU_DUAL;
-      else if (ep.act == ACT_NONE && ep.resid && ep.resid != ep.out) ek = EK_RESID;
+      // (gemm_kernel's 4-column EK_RESID rows keep no column sums: with colsum the generic kind)
+      else if (ep.act == ACT_NONE && ep.resid && ep.resid != ep.out && !ep.colsum) ek = EK_RESID;
       else if (ep.act == ACT_GELU_BWD && !ep.resid && ep.aux) ek = EK_GELU_BWD;
     }
   }
   // A-row sums (bias grad) only exist for the bf16 k-major A operand (wgrad)
-  constexpr bool RS_OK = !LA::KC && sizeof(T) == 2;
-  if (ep.rs_ptr && !RS_OK) {
+  if (ep.rs_ptr && !(!o.a_kc && o.esize == 2)) {
     hvit_set_error("launch_gemm: A row sums need a bf16 k-major A operand");
     return HVIT_ERR_ARG;
   }
@@ -1401,20 +1466,61 @@ int launch_gemm(LA la, LB lb, int M, int N, int K, int splits, const Epi& ep_in,
   // the tile, every K slice a multiple of 64, vector-aligned operands)
   // (or the implicit-im2col conv A loader, LdConvF: every 64-channel stage in
   // one tap and one source, byte offsets < 2^31 -- conv_fast_ok)
-  // Not with both operands k-major (the weight gradients): the register path
-  // measured faster there (0.82 vs 1.04 ms/step)
-  constexpr bool CONV_A = IsConvFBf16<LA>::value;
-  constexpr bool DMA_OK = sizeof(T) == 2 && (IsDenseBf16<LA>::value || CONV_A) && IsDenseBf16<LB>::value &&
-                          (LA::KC || LB::KC);
-  bool all_in = false;
-  if constexpr (DMA_OK) {
+  int stage = 0;
+  if (o.dma_ok) {
     const int bm = tile == 128 || tile == 12864 ? 128 : 64, bn = tile == 128 ? 128 : 64;
-    bool a_ok = true;  // (the conv A loader's conditions are conv_fast_ok's; the register path
-                       // for it measured slower, profiles/r2_ab/conv_dma_ab.txt)
-    if constexpr (!CONV_A) a_ok = la.vok;
-    all_in = ep.dma && M % bm == 0 && N % bn == 0 && kps % 64 == 0 && K % kps == 0 && a_ok && lb.vok &&
-             !ep.rs_ptr;
+    // (a_vok is true for the conv A loader: its conditions are conv_fast_ok's; the register
+    // path for it measured slower, profiles/r2_ab/conv_dma_ab.txt)
+    // (the LDS-DMA kernels' GELU_DUAL rows leave as 16-byte bf16 stores, epi_wide_row: an f32
+    // y or out2 takes the register-staged kernel, whose 4-column rows store either type)
+    const bool all_in = ep.dma && M % bm == 0 && N % bn == 0 && kps % 64 == 0 && K % kps == 0 && o.a_vok &&
+                        o.b_vok && !ep.rs_ptr && (ek != EK_GELU_DUAL || gelu_dual_bf16(ep));
+    if (all_in) {
+      // one-buffer LDS-DMA kernels (3 workgroups per CU, out of phase, so one's
+      // epilogue overlaps another's K loop) for the 128x128 forward kinds:
+      // vit_linear_fwd 0.732 -> 0.721 ms/step.  Not for GELU_BWD (its h
+      // prefetch spills at 168 VGPRs: dgrad 0.737 -> 0.780)
+      // conv forward (BN statistics epilogue) too: conv_fwd 0.471 -> 0.447 ms/step;
+      // not the conv data gradient (0.346 -> 0.362)
+      if (tile == 128 && (ek == EK_GELU_DUAL || ek == EK_STORE) && (!o.conv_a || ep.stats)) stage = 1;
+      // (not the conv data gradients -- implicit im2col of dy, plain store epilogue:
+      // conv_dgrad 0.376 -> 0.394 ms/step with three buffers, 72 KiB of LDS leaving
+      // two workgroups per CU where the 48 KiB two-buffer kernel keeps three; the
+      // patch-embedding forward, with its positional-row epilogue, does take them)
+      // three stage buffers from 8 stages on: two buffers 4.656-4.660 ms/step, three
+      // from 16 stages 4.543-4.551, three from 8 stages 4.509-4.524 (vit_linear_dgrad
+      // 0.784 -> 0.728, vit_linear_fwd 0.774 -> 0.741, conv_fwd 0.410 -> 0.388 ms/step)
+      else if (tile != 128 && kps / 64 >= 8 && (!o.conv_a || ep.stats || ep.rowadd)) stage = 3;
+      else stage = 2;
+    }
   }
+  p.tile = tile;
+  p.ek = ek;
+  p.stage = stage;
+  p.splits = splits;
+  p.kps = kps;
+  return HVIT_OK;
+}
+
+// q (diagnostics): only report the plan, launch nothing
+template <typename T, class LA, class LB>
+int launch_gemm(LA la, LB lb, int M, int N, int K, int splits, const Epi& ep_in, hipStream_t st,
+                int force_tile = 0, GemmPlan* q = nullptr) {
+  Epi ep = ep_in;
+  GemmPlan pl;
+  if (int rc = gemm_plan(gemm_operands<T>(la, lb), M, N, K, splits, force_tile, ep, pl)) return rc;
+  if (q) {
+    *q = pl;
+    return HVIT_OK;
+  }
+  if (pl.tile == 0) return HVIT_OK;
+  splits = pl.splits;
+  const int kps = pl.kps, tile = pl.tile, ek = pl.ek;
+  constexpr bool RS_OK = GemmPair<T, LA, LB>::RS_OK;
+  constexpr bool DMA_OK = GemmPair<T, LA, LB>::DMA_OK;
+  // set where the plan names a kernel that the branches below do not instantiate: the
+  // plan and the launch have drifted apart, and nothing is launched
+  bool no_kernel = false;
   auto go = [&](auto ekc) {
     constexpr int EKc = decltype(ekc)::value;
     auto launch = [&](auto rsc) {
@@ -1422,39 +1528,31 @@ int launch_gemm(LA la, LB lb, int M, int N, int K, int splits, const Epi& ep_in,
       auto kern = [&](auto bmc, auto bnc) {
         constexpr int BMc = decltype(bmc)::value, BNc = decltype(bnc)::value;
         dim3 g(cdiv(M, BMc), cdiv(N, BNc), splits);
+        // the LDS-DMA kernels that exist for this tile and kind (gemm_plan picks among the same)
         if constexpr (DMA_OK && !RSc) {
-          if (all_in) {
-            // one-buffer LDS-DMA kernels (3 workgroups per CU, out of phase, so one's
-            // epilogue overlaps another's K loop) for the 128x128 forward kinds:
-            // vit_linear_fwd 0.732 -> 0.721 ms/step.  Not for GELU_BWD (its h
-            // prefetch spills at 168 VGPRs: dgrad 0.737 -> 0.780)
-            // conv forward (BN statistics epilogue) too: conv_fwd 0.471 -> 0.447 ms/step;
-            // not the conv data gradient (0.346 -> 0.362)
-            if constexpr (BMc == 128 && BNc == 128 && (EKc == EK_GELU_DUAL || EKc == EK_STORE)) {
-              if (!CONV_A || ep.stats) {
-                hipLaunchKernelGGL((gemm_kernel<T, BMc, BNc, LA, LB, EKc, false, 1>), g, dim3(GEMM_THREADS), 0, st,
-                                   la, lb, M, N, K, kps, ep);
-                return;
-              }
+          if constexpr (BMc == 128 && BNc == 128 && (EKc == EK_GELU_DUAL || EKc == EK_STORE)) {
+            if (pl.stage == 1) {
+              hipLaunchKernelGGL((gemm_kernel<T, BMc, BNc, LA, LB, EKc, false, 1>), g, dim3(GEMM_THREADS), 0, st,
+                                 la, lb, M, N, K, kps, ep);
+              return;
             }
-            if constexpr (!(BMc == 128 && BNc == 128)) {
-              // (not the conv data gradients -- implicit im2col of dy, plain store epilogue:
-              // conv_dgrad 0.376 -> 0.394 ms/step with three buffers, 72 KiB of LDS leaving
-              // two workgroups per CU where the 48 KiB two-buffer kernel keeps three; the
-              // patch-embedding forward, with its positional-row epilogue, does take them)
-              // three stage buffers from 8 stages on: two buffers 4.656-4.660 ms/step, three
-              // from 16 stages 4.543-4.551, three from 8 stages 4.509-4.524 (vit_linear_dgrad
-              // 0.784 -> 0.728, vit_linear_fwd 0.774 -> 0.741, conv_fwd 0.410 -> 0.388 ms/step)
-              if (kps / 64 >= 8 && (!CONV_A || ep.stats || ep.rowadd)) {
-                hipLaunchKernelGGL((gemm_kernel<T, BMc, BNc, LA, LB, EKc, false, 3>), g, dim3(GEMM_THREADS), 0, st,
-                                   la, lb, M, N, K, kps, ep);
-                return;
-              }
+          }
+          if constexpr (!(BMc == 128 && BNc == 128)) {
+            if (pl.stage == 3) {
+              hipLaunchKernelGGL((gemm_kernel<T, BMc, BNc, LA, LB, EKc, false, 3>), g, dim3(GEMM_THREADS), 0, st,
+                                 la, lb, M, N, K, kps, ep);
+              return;
             }
+          }
+          if (pl.stage == 2) {
             hipLaunchKernelGGL((gemm_kernel<T, BMc, BNc, LA, LB, EKc, false, 2>), g, dim3(GEMM_THREADS), 0, st,
                                la, lb, M, N, K, kps, ep);
             return;
           }
+        }
+        if (pl.stage != 0) {
+          no_kernel = true;
+          return;
         }
         hipLaunchKernelGGL((gemm_kernel<T, BMc, BNc, LA, LB, EKc, RSc>), g, dim3(GEMM_THREADS), 0, st, la, lb, M, N,
                            K, kps, ep);
@@ -1477,17 +1575,25 @@ int launch_gemm(LA la, LB lb, int M, int N, int K, int splits, const Epi& ep_in,
     case EK_STORE: go(std::integral_constant<int, EK_STORE>()); break;
     case EK_GELU_DUAL:
       if constexpr (IsDenseKC<LA>::value) go(std::integral_constant<int, EK_GELU_DUAL>());
+      else no_kernel = true;
       break;
     case EK_RESID:
       if constexpr (IsDenseKC<LA>::value) go(std::integral_constant<int, EK_RESID>());
+      else no_kernel = true;
       break;
     case EK_GELU_BWD:
       if constexpr (IsDenseKC<LA>::value) go(std::integral_constant<int, EK_GELU_BWD>());
+      else no_kernel = true;
       break;
     case EK_PATCH:
       if constexpr (IsDenseKC<LA>::value) go(std::integral_constant<int, EK_PATCH>());
+      else no_kernel = true;
       break;
     default: go(std::integral_constant<int, EK_GEN>()); break;
+  }
+  if (no_kernel) {
+    hvit_set_error("launch_gemm: no kernel for the plan (tile %d, kind %d, staging %d)", tile, ek, pl.stage);
+    return HVIT_ERR_LAUNCH;
   }
   HVIT_LAUNCH_CHECK();
   return HVIT_OK;

@@ -92,6 +92,10 @@ int check_epi(const hvit_epilogue_t* e) {
   HVIT_CHECK((e->act != HVIT_ACT_GELU_DUAL && e->act != HVIT_ACT_GELU_DUAL_D && e->act != HVIT_ACT_GELU_DUAL_DK) || e->out2,
              "epilogue: GELU_DUAL needs out2");
   HVIT_CHECK((e->act != HVIT_ACT_GELU_BWD && e->act != HVIT_ACT_MUL_AUX) || e->aux, "epilogue: GELU_BWD needs aux");
+  // the GELU_DUAL family stops before the column sums: no kernel would write them
+  HVIT_CHECK(!e->colsum || (e->act != HVIT_ACT_GELU_DUAL && e->act != HVIT_ACT_GELU_DUAL_D &&
+                            e->act != HVIT_ACT_GELU_DUAL_DK && e->act != HVIT_ACT_GELU),
+             "epilogue: colsum is not defined for the GELU_DUAL family (act %d stores before the column sums)", e->act);
   HVIT_CHECK(!(e->dropout.p < 0.f || e->dropout.p >= 1.f), "epilogue: dropout p out of range");
   return HVIT_OK;
 }
@@ -242,9 +246,9 @@ bool thin_o1(const hvit_conv_geom_t* g) {
 // C[M][N] = sum_k A[m][k] B[k][n] on gemm.h's kernels: A rows K-contiguous, B
 // [K][N] (the linear and the patch-embedding data gradients; gemm_linear.hip
 // holds the one instantiation).  bad_align is the error text when N or K is
-// not a multiple of 16 bytes of dt.
+// not a multiple of 16 bytes of dt.  q (diagnostics): report the plan only.
 int hvit_gemm_kc_mn(int dt, const void* a, const void* b, int M, int N, int K, const Epi& ep, hipStream_t st,
-                    const char* bad_align);
+                    const char* bad_align, GemmPlan* q = nullptr);
 
 int hvit_thin_c1_fwd(int dt, const hvit_conv_geom_t* g, const void* w, void* y, int y_dt, float* stats, hipStream_t st);
 // split-K slabs a conv weight gradient left for its caller to reduce

@@ -2,54 +2,72 @@
 #include "gemm_host.h"
 #include "gemm_ring.h"
 
-extern "C" int hvit_linear_fwd(int dt, const void* x, const void* w, const float* bias, int M, int N, int K,
-                               void* y, int y_dt, const hvit_epilogue_t* epi, void* stream) {
-  HVIT_CHECK(x && w && y, "hvit_linear_fwd: null pointer");
+// The entry points below take q (hvit_gemm_plan): with it they run their own
+// checks and choices on the operands as given -- the GEMM operands themselves are
+// not passed and count as aligned, which the entry points require anyway -- and
+// report the kernel in *q instead of launching it; no side job runs.
+static int linear_fwd_impl(int dt, const void* x, const void* w, const float* bias, int M, int N, int K, void* y,
+                           int y_dt, const hvit_epilogue_t* epi, void* stream, GemmPlan* q) {
+  HVIT_CHECK(q || (x && w), "hvit_linear_fwd: null pointer");
+  HVIT_CHECK(y, "hvit_linear_fwd: null pointer");
   HVIT_CHECK(M >= 0 && N > 0 && K > 0, "hvit_linear_fwd: bad shape M=%d N=%d K=%d", M, N, K);
   HVIT_CHECK(aligned16(x) && aligned16(w), "hvit_linear_fwd: x/w must be 16-byte aligned");
   if (int rc = check_epi(epi)) return rc;
   HVIT_CHECK(!epi || epi->act != HVIT_ACT_RELU, "hvit_linear_fwd: RELU is a conv-forward epilogue");
   Epi ep = to_epi(epi, y, y_dt, N);
   ep.bias = bias;
-  if (int rc = take_side(epi ? &epi->side : nullptr, ep, M, (hipStream_t)stream)) return rc;
+  if (!q)
+    if (int rc = take_side(epi ? &epi->side : nullptr, ep, M, (hipStream_t)stream)) return rc;
   if (M == 0) return HVIT_OK;
   if (dt == HVIT_BF16) {
     int rc = 0;
     if (try_ring(dense<bf16_t, true>(x, K, M, K), dense<bf16_t, true>(w, K, N, K), M, N, K, 1, ep,
-                 (hipStream_t)stream, &rc))
+                 (hipStream_t)stream, &rc, -1, q))
       return rc;
   }
   DT_DISPATCH(dt, {
     HVIT_CHECK(K % Elem<T>::PER16 == 0, "hvit_linear_fwd: K=%d must be a multiple of %d", K, Elem<T>::PER16);
     return launch_gemm<T>(dense<T, true>(x, K, M, K), dense<T, true>(w, K, N, K), M, N, K, 1, ep,
-                          (hipStream_t)stream);
+                          (hipStream_t)stream, 0, q);
   });
 }
 
-extern "C" int hvit_linear_dgrad(int dt, const void* dy, const void* w, int M, int N, int K, void* dx, int dx_dt,
-                                 const hvit_epilogue_t* epi, void* stream) {
-  HVIT_CHECK(dy && w && dx, "hvit_linear_dgrad: null pointer");
+extern "C" int hvit_linear_fwd(int dt, const void* x, const void* w, const float* bias, int M, int N, int K,
+                               void* y, int y_dt, const hvit_epilogue_t* epi, void* stream) {
+  return linear_fwd_impl(dt, x, w, bias, M, N, K, y, y_dt, epi, stream, nullptr);
+}
+
+static int linear_dgrad_impl(int dt, const void* dy, const void* w, int M, int N, int K, void* dx, int dx_dt,
+                             const hvit_epilogue_t* epi, void* stream, GemmPlan* q) {
+  HVIT_CHECK(q || (dy && w), "hvit_linear_dgrad: null pointer");
+  HVIT_CHECK(dx, "hvit_linear_dgrad: null pointer");
   HVIT_CHECK(M >= 0 && N > 0 && K > 0, "hvit_linear_dgrad: bad shape");
   HVIT_CHECK(aligned16(dy) && aligned16(w), "hvit_linear_dgrad: alignment");
   if (int rc = check_epi(epi)) return rc;
   HVIT_CHECK(!epi || epi->act != HVIT_ACT_RELU, "hvit_linear_dgrad: RELU is a conv-forward epilogue");
   Epi ep = to_epi(epi, dx, dx_dt, K);
-  if (int rc = take_side(epi ? &epi->side : nullptr, ep, M, (hipStream_t)stream)) return rc;
+  if (!q)
+    if (int rc = take_side(epi ? &epi->side : nullptr, ep, M, (hipStream_t)stream)) return rc;
   if (M == 0) return HVIT_OK;
   if (dt == HVIT_BF16 && N % 8 == 0) {
     int rc = 0;
     if (try_ring(dense<bf16_t, true>(dy, N, M, N), dense<bf16_t, false>(w, K, K, N), M, K, N, 1, ep,
-                 (hipStream_t)stream, &rc))
+                 (hipStream_t)stream, &rc, -1, q))
       return rc;
   }
-  return hvit_gemm_kc_mn(dt, dy, w, M, K, N, ep, (hipStream_t)stream, "hvit_linear_dgrad: N, K alignment");
+  return hvit_gemm_kc_mn(dt, dy, w, M, K, N, ep, (hipStream_t)stream, "hvit_linear_dgrad: N, K alignment", q);
+}
+
+extern "C" int hvit_linear_dgrad(int dt, const void* dy, const void* w, int M, int N, int K, void* dx, int dx_dt,
+                                 const hvit_epilogue_t* epi, void* stream) {
+  return linear_dgrad_impl(dt, dy, w, M, N, K, dx, dx_dt, epi, stream, nullptr);
 }
 
 int hvit_gemm_kc_mn(int dt, const void* a, const void* b, int M, int N, int K, const Epi& ep, hipStream_t st,
-                    const char* bad_align) {
+                    const char* bad_align, GemmPlan* q) {
   DT_DISPATCH(dt, {
     HVIT_CHECK(N % Elem<T>::PER16 == 0 && K % Elem<T>::PER16 == 0, "%s", bad_align);
-    return launch_gemm<T>(dense<T, true>(a, K, M, K), dense<T, false>(b, N, N, K), M, N, K, 1, ep, st);
+    return launch_gemm<T>(dense<T, true>(a, K, M, K), dense<T, false>(b, N, N, K), M, N, K, 1, ep, st, 0, q);
   });
 }
 
@@ -88,7 +106,7 @@ extern "C" long long hvit_wgrad_tickets(int M, int N, int K) {
 static int linear_wgrad_impl(int dt, const void* dy, const void* x, int M, int N, int K, float* dw, float* db,
                              float* ws, long long ws_elems, unsigned* tickets, long long tickets_elems, int flags,
                              void* stream, hvit_slab_sum_t* job = nullptr,
-                             const hvit_slab_sum_t* side = nullptr);
+                             const hvit_slab_sum_t* side = nullptr, GemmPlan* q = nullptr);
 
 extern "C" int hvit_linear_wgrad(int dt, const void* dy, const void* x, int M, int N, int K, float* dw, float* db,
                                  float* ws, long long ws_elems, void* stream) {
@@ -132,8 +150,11 @@ static int slab_reduce(const float* ws, int splits, long long stride, long long 
 
 static int linear_wgrad_impl(int dt, const void* dy, const void* x, int M, int N, int K, float* dw, float* db,
                              float* ws, long long ws_elems, unsigned* tickets, long long tickets_elems, int flags,
-                             void* stream, hvit_slab_sum_t* job, const hvit_slab_sum_t* side) {
-  HVIT_CHECK(dy && x && dw, "hvit_linear_wgrad: null pointer");
+                             void* stream, hvit_slab_sum_t* job, const hvit_slab_sum_t* side, GemmPlan* q) {
+  // (q: as linear_fwd_impl's; a workspace counts as present when ws_elems > 0)
+  HVIT_CHECK(q || (dy && x), "hvit_linear_wgrad: null pointer");
+  HVIT_CHECK(dw, "hvit_linear_wgrad: null pointer");
+  const bool have_ws = q ? ws_elems > 0 : ws != nullptr;
   HVIT_CHECK(M >= 0 && N > 0 && K > 0, "hvit_linear_wgrad: bad shape");
   HVIT_CHECK(aligned16(dy) && aligned16(x), "hvit_linear_wgrad: alignment");
   hipStream_t st = (hipStream_t)stream;
@@ -143,7 +164,7 @@ static int linear_wgrad_impl(int dt, const void* dy, const void* x, int M, int N
   if (int rc = take_side(side, sj, M, st)) return rc;
   const long long NK = (long long)N * K;
   int splits = wgrad_splits(N, K, M, LIN_WG_BM, LIN_WG_BN);
-  if ((long long)splits * (NK + N) > ws_elems || !ws) splits = 1;
+  if ((long long)splits * (NK + N) > ws_elems || !have_ws) splits = 1;
   auto side_alone = [&]() -> int {
     if (!sj.sj_n4) return HVIT_OK;
     const int r = hvit_sum_slabs_strided(sj.sj_src, sj.sj_splits, sj.sj_stride4 * 4, sj.sj_n4 * 4, sj.sj_dst, stream);
@@ -158,6 +179,7 @@ static int linear_wgrad_impl(int dt, const void* dy, const void* x, int M, int N
     e.sj_splits = sj.sj_splits;
   };
   if (M == 0) {
+    if (q) return HVIT_OK;
     if (int rc = side_alone()) return rc;
     (void)hipMemsetAsync(dw, 0, sizeof(float) * NK, st);
     if (db) (void)hipMemsetAsync(db, 0, sizeof(float) * N, st);
@@ -167,6 +189,7 @@ static int linear_wgrad_impl(int dt, const void* dy, const void* x, int M, int N
   // over a chunk of rows
   if (!tickets && hvit_wgrad_small_ok(dt, M, N, K) && (!db || db == dw + NK) &&
       ws_elems >= hvit_wgrad_small_ws(M, N, K)) {
+    if (q) return HVIT_OK;  // (the tall-skinny kernel, no GEMM tile: the plan stays empty)
     if (int rc = side_alone()) return rc;
     return hvit_wgrad_small(dy, x, M, N, K, dw, db, ws, ws_elems, stream, job);
   }
@@ -176,7 +199,7 @@ static int linear_wgrad_impl(int dt, const void* dy, const void* x, int M, int N
   if (dt == HVIT_BF16 && !fused_db && N % 8 == 0 && K % 8 == 0 && rcfg > 0) {
     const RingCfg r = ring_cfg(rcfg);
     int s = wgrad_splits(N, K, M, r.bm, r.bn);
-    if ((long long)s * (NK + N) > ws_elems || !ws) s = 1;
+    if ((long long)s * (NK + N) > ws_elems || !have_ws) s = 1;
     s = plan_splits<bf16_t>(M, s);
     Epi e;
     e.out_dt = HVIT_F32;
@@ -190,11 +213,12 @@ static int linear_wgrad_impl(int dt, const void* dy, const void* x, int M, int N
     if (tk) {
       e.tickets = tickets;
       e.red_out = dw;
-      if (!(flags & HVIT_ACC_ZEROED)) (void)hipMemsetAsync(tickets, 0, sizeof(unsigned) * (N / r.bm) * (K / r.bn), st);
+      if (!q && !(flags & HVIT_ACC_ZEROED)) (void)hipMemsetAsync(tickets, 0, sizeof(unsigned) * (N / r.bm) * (K / r.bn), st);
     }
     int rc = 0;
-    if (try_ring(dense<bf16_t, false>(dy, N, N, M), dense<bf16_t, false>(x, K, K, M), N, K, M, s, e, st, &rc, rcfg)) {
-      if (rc) return rc;
+    if (try_ring(dense<bf16_t, false>(dy, N, N, M), dense<bf16_t, false>(x, K, K, M), N, K, M, s, e, st, &rc, rcfg,
+                 q)) {
+      if (rc || q) return rc;
       if (s > 1 && !tk)
         if (int rc2 = slab_reduce(ws, s, NK + N, NK, dw, stream, job)) return rc2;
       // (the slabs are consumed on the stream before this reuses ws; a deferred job
@@ -218,8 +242,8 @@ static int linear_wgrad_impl(int dt, const void* dy, const void* x, int M, int N
       ep.rs_stride = splits > 1 ? NK + N : 0;
     }
     int rc = launch_gemm<T>(dense<T, false>(dy, N, N, M), dense<T, false>(x, K, K, M), N, K, M, splits, ep, st,
-                            LIN_WG_TILE);
-    if (rc) return rc;
+                            LIN_WG_TILE, q);
+    if (rc || q) return rc;
   });
   if (splits > 1) {
     // sums [dw | db] when fused (db follows dw), else dw alone
@@ -227,6 +251,35 @@ static int linear_wgrad_impl(int dt, const void* dy, const void* x, int M, int N
       return rc;
   }
   if (db && !fused_db) return hvit_reduce_rows_ws(dy, dt, M, N, N, 0, db, job ? nullptr : ws, ws_elems, stream);
+  return HVIT_OK;
+}
+
+// Diagnostics: which kernel the entry point would launch, from the entry points' own code
+// (their *_impl with q set: same checks, same ring_plan / gemm_plan calls, no launch)
+extern "C" int hvit_gemm_plan(int entry, int dt, int M, int N, int K, const float* bias, const void* out, int out_dt,
+                              const hvit_epilogue_t* epi, long long ws_elems, hvit_gemm_plan_t* plan) {
+  HVIT_CHECK(plan, "hvit_gemm_plan: null plan");
+  GemmPlan q;
+  int rc;
+  switch (entry) {
+    case HVIT_PLAN_LINEAR_FWD:
+      rc = linear_fwd_impl(dt, nullptr, nullptr, bias, M, N, K, (void*)out, out_dt, epi, nullptr, &q);
+      break;
+    case HVIT_PLAN_LINEAR_DGRAD:
+      rc = linear_dgrad_impl(dt, nullptr, nullptr, M, N, K, (void*)out, out_dt, epi, nullptr, &q);
+      break;
+    case HVIT_PLAN_LINEAR_WGRAD:
+      rc = linear_wgrad_impl(dt, nullptr, nullptr, M, N, K, (float*)out, (float*)bias, nullptr, ws_elems, nullptr, 0, 0,
+                             nullptr, nullptr, nullptr, &q);
+      break;
+    default: hvit_set_error("hvit_gemm_plan: bad entry %d", entry); return HVIT_ERR_ARG;
+  }
+  if (rc) return rc;
+  plan->ring = q.ring;
+  plan->tile = q.tile;
+  plan->epi_kind = q.ek;
+  plan->staging = q.stage;
+  plan->splits = q.tile ? q.splits : 0;
   return HVIT_OK;
 }
 

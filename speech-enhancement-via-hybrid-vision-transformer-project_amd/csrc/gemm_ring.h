@@ -344,20 +344,18 @@ int launch_ring(int cfg, const LdDense<bf16_t, KCA>& la, const LdDense<bf16_t, K
 // The ring path applies to dense bf16 operands with every tile interior:
 // M % BM == N % BN == 0, K slices of whole 64-deep stages, 16-byte aligned
 // operands / outputs with ld % 8 == 0, byte extents < 2^31.
-template <bool KCA, bool KCB>
-bool ring_ok(int cfg, const LdDense<bf16_t, KCA>& la, const LdDense<bf16_t, KCB>& lb, int M, int N, int kps,
-             int K, const Epi& ep) {
+inline bool ring_ok(int cfg, const GemmOperands& o, int M, int N, int kps, int K, const Epi& ep) {
   if (cfg <= 0) return false;
   const RingCfg rc = ring_cfg(cfg);
   if (M % rc.bm || N % rc.bn || kps % 64 || K % kps) return false;
-  if (!la.vok || !lb.vok || !ep.vec_ok) return false;
+  if (!o.a_vok || !o.b_vok || !ep.vec_ok) return false;
   if ((ep.ldo & 7) || (ep.out2 && (ep.ldo2 & 7)) || (ep.aux && (ep.ldaux & 7))) return false;
   if (ep.rowadd || ep.stats || ep.rs_ptr || ep.act == ACT_TANH || ep.relu || ep.mode == EPI_SPLIT2 ||
       ep.mode == EPI_PATCH)
     return false;
   auto al = [](const void* p) { return !p || (((uintptr_t)p) & 15) == 0; };
   if (!al(ep.out) || !al(ep.out2) || !al(ep.aux) || !al(ep.resid) || !al(ep.bias)) return false;
-  return dense_bytes(la) < (1L << 31) && dense_bytes(lb) < (1L << 31);
+  return o.a_bytes < (1L << 31) && o.b_bytes < (1L << 31);
 }
 
 // the configuration the linear entry points use (-1 automatic; hvit_ring_tune
@@ -385,13 +383,13 @@ inline int ring_pick(bool kca, bool kcb, int M, int N, int K) {
 
 // Dense bf16 GEMM through the ring kernels when they apply (returns false
 // otherwise, and the caller takes gemm.h's launch_gemm).
-template <bool KCA, bool KCB>
-bool try_ring(const LdDense<bf16_t, KCA>& la, const LdDense<bf16_t, KCB>& lb, int M, int N, int K, int splits,
-              const Epi& ep_in, hipStream_t st, int* rc_out, int cfg = -1) {
+// The ring path's whole choice (gemm.h's GemmPlan): true where a ring kernel
+// takes the call, with ep completed and p filled; false where gemm.h's
+// launch_gemm does.  cfg < 0: the knob's configuration, or the automatic one.
+inline bool ring_plan(const GemmOperands& o, int M, int N, int K, int splits, int cfg, Epi& ep, GemmPlan& p) {
   if (cfg < 0) cfg = ring_default_cfg();
-  if (cfg < 0) cfg = ring_pick(KCA, KCB, M, N, K);
+  if (cfg < 0) cfg = ring_pick(o.a_kc, o.b_kc, M, N, K);
   if (cfg == 0) return false;
-  Epi ep = ep_in;
   if (ep.slab_stride == 0) ep.slab_stride = (long)M * ep.ldo;
   ep.xcd_remap = 1;
   auto vok = [](const void* p, long ld) { return !p || ((((uintptr_t)p) & 15) == 0 && ld % 8 == 0); };
@@ -399,7 +397,7 @@ bool try_ring(const LdDense<bf16_t, KCA>& la, const LdDense<bf16_t, KCB>& lb, in
               vok(ep.resid, ep.ldr);
   int kps = 0;
   splits = plan_splits<bf16_t>(K, splits, &kps);
-  if (!ring_ok(cfg, la, lb, M, N, kps, K, ep)) return false;
+  if (!ring_ok(cfg, o, M, N, kps, K, ep)) return false;
   int ek;
   if (ep.mode == EPI_SLAB) ek = EK_SLAB;
   else if (splits > 1) return false;
@@ -410,23 +408,60 @@ bool try_ring(const LdDense<bf16_t, KCA>& la, const LdDense<bf16_t, KCB>& lb, in
   else return false;
   if (ek == EK_STORE && (ep.drop_thr || ep.drop_scale != 1.f)) return false;
   if ((ek == EK_GELU_DUAL || ek == EK_RESID || ek == EK_GELU_BWD) && !ep.drop_thr && ep.drop_scale != 1.f) return false;
+  // (epi_wide_row's GELU_DUAL rows are bf16 stores)
+  if (ek == EK_GELU_DUAL && !gelu_dual_bf16(ep)) return false;
+  // the kinds' kernels exist for a k-contiguous A (GELU_BWD) or both operands (GELU_DUAL, RESID)
+  if (ek == EK_GELU_BWD && !o.a_kc) return false;
+  if ((ek == EK_GELU_DUAL || ek == EK_RESID) && !(o.a_kc && o.b_kc)) return false;
+  p = GemmPlan();
+  p.ring = cfg;
+  p.tile = cfg == 4 ? 256 : cfg == 5 ? 12864 : 128;
+  p.ek = ek;
+  p.stage = 2;
+  p.splits = splits;
+  p.kps = kps;
+  return true;
+}
+
+// ring_plan chose a kind that try_ring has no kernel for: the plan and the launch have
+// drifted apart (an error, never a silent move to launch_gemm under another plan)
+inline int ring_no_kernel(int ek) {
+  hvit_set_error("try_ring: no ring kernel for epilogue kind %d with these operand layouts", ek);
+  return HVIT_ERR_LAUNCH;
+}
+
+// q (diagnostics): only report the plan, launch nothing
+template <bool KCA, bool KCB>
+bool try_ring(const LdDense<bf16_t, KCA>& la, const LdDense<bf16_t, KCB>& lb, int M, int N, int K, int splits,
+              const Epi& ep_in, hipStream_t st, int* rc_out, int cfg = -1, GemmPlan* q = nullptr) {
+  Epi ep = ep_in;
+  GemmPlan pl;
+  if (!ring_plan(gemm_operands<bf16_t>(la, lb), M, N, K, splits, cfg, ep, pl)) return false;
+  if (q) {
+    *q = pl;
+    *rc_out = HVIT_OK;
+    return true;
+  }
+  cfg = pl.ring;
+  splits = pl.splits;
+  const int kps = pl.kps, ek = pl.ek;
   int rc = HVIT_OK;
   switch (ek) {
     case EK_SLAB: rc = launch_ring<KCA, KCB, EK_SLAB>(cfg, la, lb, M, N, K, splits, kps, ep, st); break;
     case EK_STORE: rc = launch_ring<KCA, KCB, EK_STORE>(cfg, la, lb, M, N, K, splits, kps, ep, st); break;
     case EK_GELU_BWD:
       if constexpr (KCA) rc = launch_ring<KCA, KCB, EK_GELU_BWD>(cfg, la, lb, M, N, K, splits, kps, ep, st);
-      else return false;
+      else rc = ring_no_kernel(ek);  // (ring_plan admits the kind for these layouts only)
       break;
     case EK_GELU_DUAL:
       if constexpr (KCA && KCB) rc = launch_ring<KCA, KCB, EK_GELU_DUAL>(cfg, la, lb, M, N, K, splits, kps, ep, st);
-      else return false;
+      else rc = ring_no_kernel(ek);  // (ring_plan admits the kind for these layouts only)
       break;
     case EK_RESID:
       if constexpr (KCA && KCB) rc = launch_ring<KCA, KCB, EK_RESID>(cfg, la, lb, M, N, K, splits, kps, ep, st);
-      else return false;
+      else rc = ring_no_kernel(ek);  // (ring_plan admits the kind for these layouts only)
       break;
-    default: return false;
+    default: rc = ring_no_kernel(ek); break;
   }
   *rc_out = rc;
   return true;
